@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the composite-likelihood hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
 
 A "step" is one optimiser epoch of the reference's `train_quantization`
 (cherryml/estimation/_ratelearn/trainer.py:156-218) over one synthetic bank:
@@ -88,6 +88,35 @@ F32_PEAK_TFLOPS = 157.3    # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32 / 32x32
 LDS_ATOMIC_PEAK_G = 9830.4  # G lane-atomics/s: 16 lanes per clock per CU (LDS table: a 4-byte LDS write / atomic = 4 cycles per
                             # wave-instruction) x 256 CUs x 2.4 GHz, conflict-free
 L2_GATHER_PEAK_GBS = 16800.0  # MI355X_MICROARCH.md, "Indexed rows": rows gathered from a table shared in the XCD's L2, chip-wide
+
+# --dump-outputs DIR: every line's timed path hands back what its last step computed (the arrays its caller receives), read
+# back after the timed region; main writes them as DIR/<name>.npy (headline) and DIR/<line>__<name>.npy (secondary lines)
+DUMP_OUTPUTS = False
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 19      # entries of a fixed, seeded sample of a count tensor too large to write whole
+DUMP_SEED = 2024
+
+
+def _dump_large(name, t):
+    """A device tensor too large to dump whole: DUMP_SAMPLE entries at fixed seeded positions (the same for every run of
+    the same shape) and its sums over the last axis, float64."""
+    import torch
+    flat = t.reshape(-1)
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=DUMP_SAMPLE))
+    return {name + "_sample": flat[torch.from_numpy(idx).to(flat.device)].double().cpu().numpy(),
+            name + "_sum_last_axis": t.double().sum(-1).cpu().numpy()}
+
+
+def write_outputs(path, outputs):
+    """DIR/<name>.npy for every dumped array (float64; float32 stays float32), at most DUMP_LIMIT_BYTES in all."""
+    arrays = {k: np.asarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64)
+              for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 # --------------------------------------------------------------------- inputs
@@ -361,7 +390,13 @@ def main():
     ap.add_argument("--torch-glue", action="store_true",
                     help="multi-GPU co-evolution: keep theta->Q / Adam in torch and the collective in "
                          "torch.distributed instead of the C-driven loop with the in-library ncclAllReduce")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what each line's timed path computed in its last step as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB in all; large count tensors as a fixed seeded "
+                         "sample); the inputs are the same from run to run, so two builds can be compared output for output")
     args = ap.parse_args()
+    global DUMP_OUTPUTS
+    DUMP_OUTPUTS = args.dump_outputs is not None
 
     if args.gpus is None:   # left at its default: adopt the launcher's rank count (an EXPLICIT mismatch is still refused below)
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
@@ -489,6 +524,7 @@ def main():
                 tm = bank.timing_means()
                 bank.profile(False)
                 final_loss = float(r["loss"][-1])
+                outputs = {k: r[k] for k in ("loss", "Q_best", "Q_last")}
             else:
                 opt = torch.optim.Adam(module.parameters(), lr=0.1)
                 glue = "theta->Q and Adam in torch, loss + dL/dQ in HIP"
@@ -512,6 +548,9 @@ def main():
                 tm = bank.timing_means()
                 bank.profile(False)
                 final_loss = float(last.item())
+                # (the module's parameters after the last Adam step, and the loss that step evaluated)
+                outputs = ({"loss": np.array([final_loss]), "Q_last": module().detach().cpu().numpy()}
+                           if DUMP_OUTPUTS else None)
             kernel_ms = None
             bank = sharded   # closed below (bank + communicator)
         else:
@@ -571,6 +610,8 @@ def main():
             bank.profile(False)
             final_loss = float(np.sum(r["loss"][-1]) if "loss" in r
                                else np.sum(r["loss_per_epoch_per_site"][-1]))
+            outputs = ({k: r[k] for k in ("loss", "Q_best", "Q_last")} if "loss" in r
+                       else {"loss_per_site": r["loss_per_epoch_per_site"][-1], "Q_best_per_site": r["res"]})
         tm_max, rccl_ranks = None, None
         if world > 1 or args.force_sharded or shard_of:
             rccl_ranks = getattr(getattr(bank, "rccl", None), "count", None)   # ncclCommCount of the raw communicator
@@ -765,6 +806,7 @@ def main():
                if S > 32 and steps >= 2 * PHASE_EVENTS_EVERY else {}),
             **({"bank_form": bank_form} if bank_form else {}),
             "final_loss": final_loss,
+            **({"_outputs": outputs} if DUMP_OUTPUTS else {}),
         }
         if resumed and prewarm_ms is not None:
             # the throw-away optimisation in front of the warm-up takes the one-off costs of a fresh process out of
@@ -826,7 +868,10 @@ def main():
             ctypes.CDLL(None).fflush(None)
         except Exception:
             pass
+        outputs = out.pop("_outputs", {}) if out is not None else {}
         if rank == 0:
+            if args.dump_outputs is not None:
+                write_outputs(args.dump_outputs, outputs)
             sys.stdout.write(json.dumps(out) + "\n")
             sys.stdout.flush()
 
@@ -896,6 +941,8 @@ def main():
         if rank == 0:
             for name, sec in extra.items():
                 if sec is not None:
+                    for k, v in sec.pop("_outputs", {}).items():
+                        out.setdefault("_outputs", {})[f"{name}__{k}"] = v
                     out[name] = {k: sec[k] for k in keep + ("latency_budget", "phase_ms_max_over_ranks") if k in sec}
     finish(out)
 
@@ -991,6 +1038,8 @@ def run_counting(steps, warmup, world, rank, local_rank, fence, with_cpu):
                              "of every atomic (~25 % of the pass) and the slab write + reduction"},
         "counted_pairs": counted,
     }
+    if DUMP_OUTPUTS:   # the [B, S, S] histogram of the last pass
+        out["_outputs"] = {"counts": d_counts.double().reshape(B, S, S).cpu().numpy()}
     if with_cpu:
         from oracle import counting_oracle as co
         npairs = 150
@@ -1129,6 +1178,8 @@ def run_co_counting(steps, warmup, world, rank, local_rank, fence, with_cpu, fam
         "phase_ms": {"count": kernel_ms, "allreduce": float(np.mean(ams))},
         "counted_events": counted,
     }
+    if DUMP_OUTPUTS:   # the [B, 400, 400] histogram of the last pass (165 MB): a seeded sample and its row sums
+        out["_outputs"] = _dump_large("counts", d_counts.reshape(B, S2, S2))
     if with_cpu:
         from oracle import counting_oracle as co
         npairs = 40
@@ -1240,6 +1291,8 @@ def run_ble(steps, warmup, world, rank, local_rank, fence, with_cpu):
                              "including its one-off bank kernels; wave-uniform bisection with a wavefront reduction per step: "
                              "the dependent gather -> reduce -> compare chain, not bandwidth, sets the time"},
     }
+    if DUMP_OUTPUTS:   # what the last call returned: a branch length per cherry, a rate per site
+        out["_outputs"] = {"lengths": lengths, "site_rates": srates}
     if with_cpu:
         from oracle import ble_oracle as bo
         if bo.ref_available():
@@ -1304,6 +1357,8 @@ def run_assembly(steps, warmup, world, rank, local_rank, fence, with_cpu):
                      "frac": nbytes / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None, "bytes_per_step": nbytes,
                      "note": "the [L,B,S,S] tensor is cleared (1 write) and its live (site, bucket) matrices rewritten"},
     }
+    if DUMP_OUTPUTS:   # the [L, B, S, S] count tensor of the last assembly (211 MB): a seeded sample and its row sums
+        out["_outputs"] = _dump_large("counts", out_t)
     if with_cpu:
         from oracle import siterm_assembly_oracle as sa
         sub = 64
@@ -1481,6 +1536,8 @@ def run_likelihood(steps, warmup, world, rank, local_rank, fence, with_cpu):
                              "nodes read their P_v (1.28 MB) once per 32-pair block (tl_mfma_kernel); the transition bank "
                              "(config.bank_ms) holds the internal nodes only"},
     }
+    if DUMP_OUTPUTS:   # what the last call returned: the family's log-likelihood and its per-site terms
+        out["_outputs"] = {"log_likelihood": np.array([ll]), "log_likelihood_per_site": np.asarray(lls)}
     if with_cpu:
         from oracle import likelihood_oracle as lo
         srng = np.random.default_rng(7)

@@ -1,21 +1,15 @@
 """FastCherries host side (no GPU): the seeded divide-and-conquer pairing and the initial site-rate
-weights against vectors produced by the reference's own C++ (tests/golden/make_golden_fast_cherries.py,
-oracle/_ref/libref_fc.so), and -- where that library is present -- against the compiled reference
-directly on fresh random inputs."""
-import ctypes as C
-import os
-
+weights against vectors produced by the reference's own C++ (tests/golden/make_golden_fast_cherries.py and
+make_golden_ref_native.py, oracle/_ref/libref_fc.so)."""
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
+from conftest import load_golden
 
 from cherryml_amd.phylogeny_estimation._fast_cherries import (_Mt19937, _through_text, _uniform_index,
                                                               cherries_to_tree, divide_and_pair,
                                                               get_weights_for_initial_site_rates,
                                                               rate_categories_ble)
-
-REF = os.path.join(ROOT, "oracle", "_ref", "libref_fc.so")
 
 
 def test_mersenne_twister_is_std_mt19937():
@@ -68,27 +62,19 @@ def test_text_round_trip_and_tree_rule():
                          ("root", "d", 1.0)]
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref/libref_fc.so not built (needs /root/reference)")
 def test_pairing_and_weights_against_the_compiled_reference():
-    lib = C.CDLL(REF)
-    rng = np.random.default_rng(123)
+    """Outputs of the compiled reference (oracle/_ref/libref_fc.so) on 25 random families, stored by
+    tests/golden/make_golden_ref_native.py."""
+    z = load_golden("ref_native.npz")
     for trial in range(25):
-        n, L = int(rng.integers(2, 120)), int(rng.integers(1, 50))
-        seqs = np.tile(rng.integers(0, 20, size=L), (n, 1))
-        flip = rng.random((n, L)) < rng.uniform(0.02, 0.7)
-        seqs[flip] = rng.integers(0, 20, size=int(flip.sum()))
-        seqs[rng.random((n, L)) < 0.15] = -1
-        s32 = np.ascontiguousarray(seqs, dtype=np.int32)
-        out = np.zeros(2 * n, dtype=np.int32)
-        m = lib.ref_divide_and_pair(s32.ctypes.data_as(C.c_void_p), n, L, 7 + trial, out.ctypes.data_as(C.c_void_p))
-        want = [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(m)]
-        assert divide_and_pair(seqs, seed=7 + trial) == want
-        assert divide_and_pair(seqs, seed=7 + trial, _force_python=True) == want
+        seqs = z[f"pair{trial}_seqs"].astype(np.int64)
+        seed = int(z[f"pair{trial}_seed"])
+        want = [(int(a), int(b)) for a, b in z[f"pair{trial}_pairs"]]
+        assert divide_and_pair(seqs, seed=seed) == want
+        assert divide_and_pair(seqs, seed=seed, _force_python=True) == want
         if trial < 5:   # the older libstdc++ rule: both of our routes agree with each other
             assert (divide_and_pair(seqs, seed=3, rng_scheme="gcc10")
                     == divide_and_pair(seqs, seed=3, rng_scheme="gcc10", _force_python=True))
     for R in (2, 5, 20, 41):
         r = np.array(rate_categories_ble(R))
-        w = np.zeros(R)
-        lib.ref_initial_weights(r.ctypes.data_as(C.c_void_p), R, w.ctypes.data_as(C.c_void_p))
-        assert np.array_equal(np.array(get_weights_for_initial_site_rates(r)), w)
+        assert np.array_equal(np.array(get_weights_for_initial_site_rates(r)), z[f"w{R}"])

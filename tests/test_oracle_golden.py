@@ -138,24 +138,16 @@ def test_jtt_ipw_reference_goldens():
 
 def test_oracle_expm_against_reference_native_pade():
     """oracle/_ref/libref_expm.so = the reference's vendored r8mat_expm1 (Pade, FastCherries'
-    bank: io_helpers.cpp:150-174), built from the reference's own sources by oracle/Makefile.
+    bank: io_helpers.cpp:150-174), built from the reference's own sources by oracle/Makefile; its
+    outputs are stored by tests/golden/make_golden_ref_native.py.
     Cross-checks the oracle's expm (torch.matrix_exp, f64) on the LG matrix over the grid."""
-    import ctypes
-    import os
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                        "oracle", "_ref", "libref_expm.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref not built (needs /root/reference: `make -C oracle`)")
-    lib = ctypes.CDLL(path)
-    lib.ref_expm.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     Q = load_golden("data_lg.npz")["lg"]
+    z = load_golden("ref_native.npz")
     grid = np.array([float("%.8f" % (0.03 * 1.1 ** i)) for i in range(-64, 65)])[::8]
+    assert np.array_equal(grid, z["expm_grid"])
     P = orc.expm_bank(Q, grid)
-    for b, t in enumerate(grid):
-        A = np.asfortranarray(t * Q)
-        out = np.empty((20, 20), order="F")
-        assert lib.ref_expm(20, A.ctypes.data, out.ctypes.data) == 0
-        assert np.abs(np.ascontiguousarray(out) - P[b]).max() < 5e-14
+    for b in range(len(grid)):
+        assert np.abs(z["expm_P"][b] - P[b]).max() < 5e-14
 
 
 # ---- SiteRM count / pseudocount assembly (SURVEY 8f #4) -------------------------------------
@@ -227,8 +219,10 @@ def test_ble_oracle_against_compiled_reference_outputs(k):
     lengths, site_rates, _, _ = bo.ble(cx, cy, np.concatenate([cx, cy]), bank, grid, rates, z[f"rnd{k}_weights"], 50)
     assert np.array_equal(lengths, z[f"rnd{k}_ble_lengths"])
     assert np.array_equal(site_rates, z[f"rnd{k}_ble_rates"])
-    if bo.ref_available():   # the bank itself against the reference's native Pade expm
-        assert np.allclose(bank, bo.ref_log_bank(z["Q"], grid, rates), rtol=1e-9, atol=1e-12)
+    # the bank itself against the reference's native Pade expm (make_golden_ref_native.py: 2048 entries of the whole
+    # [T,R,S,S] bank at seeded positions)
+    zr = load_golden("ref_native.npz")
+    assert np.allclose(bank.reshape(-1)[zr[f"rnd{k}_bank_idx"]], zr[f"rnd{k}_bank"], rtol=1e-9, atol=1e-12)
 
 
 def test_siterm_site_rate_gather_oracle():
