@@ -90,8 +90,13 @@ int cb_tb_prepare_ew(int B, int ns, int ng, size_t *cache);
 int cb_tb_launch_ew(const CbTbEwArgs &a, hipStream_t stream, hipEvent_t stop, int *nparts);
 
 // Test hooks (tests/, profiles/): environment variables that change WHICH kernels run or inject faults are honoured only
-// when CB_TEST_HOOKS=1 is set as well -- a stray CB_NO_SYM in a user's shell must not change the path.  (CB_DEBUG and
-// CB_TRACE_SLOW only log; CB_BANK_STREAMS is a documented opt-in.)
+// when CB_TEST_HOOKS=1 is set as well -- a stray CB_NO_SYM in a user's shell must not change the path.  The complete list:
+//   bank forms of the large path (cherrybank.hip, choose_large_form): CB_BANK_TB, CB_BANK_FUSED, CB_BANK_UNFUSED, CB_BANK_K3,
+//     CB_BANK_KG, CB_BANK_TEST_NO_CLAIM, CB_PHI_Z;
+//   time basis maintenance (cherrybank.hip): CB_TB_TEST_GROWTH, CB_TB_TEST_WARN;
+//   eigensolver (train_host.hip.h, eigh_large_host.hip.h): CB_EIGH_HOST, CB_NO_HYBRID, CB_EIGH_SHORT_PLAN;
+//   counts (create_host.hip.h): CB_NO_SYM;   faults (cherrybank.hip, train_host.hip.h): CB_FAULT_INJECT.
+// (CB_DEBUG and CB_TRACE_SLOW only log; CB_BANK_STREAMS is a documented opt-in.)
 static inline const char *cb_test_hook(const char *name) {
   const char *on = getenv("CB_TEST_HOOKS");
   return (on && on[0] == '1') ? getenv(name) : nullptr;

@@ -266,370 +266,378 @@ static int tb_maintain(cb_bank *h, int B, int epoch, double two_sigma, bool stal
   return CB_OK;
 }
 
-// h->A (padded, symmetric) and h->dsq are filled.  Output: dQ (S x S, dQ = D^1/2 dA D^-1/2) when
-// `dA_padded` is false, else dL/dA itself as a padded LD x LD matrix.
-// `plan`: a warm solve enqueued as a device-controlled plan (eigh_planned_host.hip.h) instead of the host-driven loop; the
-// caller reads the record of solve `h->eseq` afterwards and repeats the evaluation without a plan if the solve stalled.
-static int large_eval(cb_bank *h, bool normalize, double *lossd, double *out, bool dA_padded, double *Pd,
-                      bool reuse_eigh = false, const EighPlan *plan = nullptr, int plan_first_slot = 0) {
-  const int S = h->S, LD = h->LD;
-  const int B = Pd ? h->B : h->Bl;                 // the loss visits live buckets only
-  const double *tb = Pd ? h->t : h->t_live;
-  const size_t LL = (size_t)LD * LD;
-  double *dQd = out;
-  int rc = CB_OK;
-  const bool planned_now = plan && h->have_prev;
-  static const int n_parts = getenv("CB_BANK_STREAMS") ? std::min(4, std::max(1, atoi(getenv("CB_BANK_STREAMS")))) : 1;
+// ---------------------------------------------------------------- bank forms of the large path
+// Which form the bank of one evaluation takes.  choose_large_form() fills it from the shape and the handle; large_eval corrects
+// `tb` once the solve is done (the host-side range check) and then reports the form that ran (cb_last_bank_form).
+struct LargeBankForm {
+  bool tb = false;        // the bank in a time basis (tbasis.hip.h)
+  // the per-bucket form (the one that runs when `tb` is off, or is switched off after the solve):
+  bool fused = false;     // K1 -> K2 -> K3 as one persistent launch (k123_bank)
+  bool accum = false;     // the buckets summed before the last product (ky_reduce_loss / kphi_combine) instead of K3
+  int kg = 1;             // tile form of K1 .. K3: four-wave (1) or eight-wave (2) workgroups
+  int n_parts = 1;        // CB_BANK_STREAMS: the separate launches in n parts on n queues
+  int tiles_k3 = 0;       // K3 tiles per bucket (0 with `accum`)
+  int test_no_claim = 0;  // (tests/test_gpu_s400_full.py: k123_bank's help path)
+  double phi_delta = 0;   // the bucket-sum tail's series threshold
+};
+
+// `want_grad`: dL/dQ is wanted (not the loss alone); `planned_now`: the solve in front is a device-controlled plan.
+// The test hooks are read per call (the tests switch them inside one process).
+static LargeBankForm choose_large_form(const cb_bank *h, int B, bool Pd, bool want_grad, bool planned_now) {
+  // OPT-IN (CB_BANK_STREAMS=n, float64 bank, no profile markers): the buckets in n equal parts on n queues, K1 -> K2 -> K3 each,
+  // so that the drain of one part's kernel overlaps the other parts' kernels; same results bit for bit (disjoint buckets, the
+  // bucket sum is taken after the join).  n = 2: 1.110 -> 1.072 ms per epoch on the bench bank; 3 and 4 are slower again.  Not
+  // the default: with kernels of two queues sharing the chip the per-kernel durations the bench reports (HIP events on one
+  // stream, rocprof averages) stop meaning anything.  Any n > 1 rules out the time basis, the fused launch and the bucket sum.
+  static const int streams = getenv("CB_BANK_STREAMS") ? std::min(4, std::max(1, atoi(getenv("CB_BANK_STREAMS")))) : 1;
+  const char *tb_hook = cb_test_hook("CB_BANK_TB"), *fused_hook = cb_test_hook("CB_BANK_FUSED"),
+             *unfused_hook = cb_test_hook("CB_BANK_UNFUSED"), *k3_hook = cb_test_hook("CB_BANK_K3"),
+             *kg_hook = cb_test_hook("CB_BANK_KG"), *no_claim_hook = cb_test_hook("CB_BANK_TEST_NO_CLAIM"),
+             *phi_z_hook = cb_test_hook("CB_PHI_Z");
+  const int LD = h->LD, tm = (LD + LG_TM - 1) / LG_TM, tn = (LD + LG_TN - 1) / LG_TN;
+  const bool f32 = h->dtype == CB_F32 && !Pd;
+  LargeBankForm f;
   // The bank in a TIME BASIS (tbasis.hip.h): float64 banks with symmetric counts from CB_TB_MIN_B live buckets on; CB_BANK_TB=0 / 1
   // forces it off / on (test hook), CB_PER_BUCKET_PRODUCTS at cb_create keeps every bucket's own products.  Behind a planned
-  // solve the basis is the one the trainer kept in range with the previous epoch's sigma (lge_norms guards this epoch's: EC_SKIP);
-  // otherwise the host reads sigma below (the host-driven solver has waited for the device several times by then).
+  // solve the basis is the one the trainer kept in range with the previous epoch's sigma (lge_norms guards this epoch's: EC_SKIP),
+  // so a basis built for another grid rules it out; otherwise the host reads sigma after the solve (the host-driven solver has
+  // waited for the device several times by then).
   // A rank of a sharded job runs ITS buckets in its own basis (every N-th bucket of an ascending grid is one; the partial sums it
   // all-reduces are linear in its G_b whatever the form); sigma, hence every rebuild and repeat decision, is the same on all ranks.
   // (a test hook that pins one of the per-bucket forms -- CB_BANK_FUSED / _UNFUSED / _K3 / _KG / _TEST_NO_CLAIM -- means those forms)
-  const char *tb_hook = cb_test_hook("CB_BANK_TB");
-  const bool form_hooks = cb_test_hook("CB_BANK_FUSED") || cb_test_hook("CB_BANK_UNFUSED") || cb_test_hook("CB_BANK_K3") ||
-                          cb_test_hook("CB_BANK_KG") || cb_test_hook("CB_BANK_TEST_NO_CLAIM");
-  bool use_tb = h->sym_counts && !h->per_bucket_products && !h->tb_block && !h->tb_failed && !Pd && dQd != nullptr && h->tb_Ls[0] &&
-                n_parts == 1 && (h->dtype == CB_F64 || h->dtype == CB_MIXED) &&
-                (tb_hook ? atoi(tb_hook) != 0 : (!form_hooks && B >= CB_TB_MIN_B));
-  if (use_tb && planned_now && h->tb.B != B) use_tb = false;
+  const bool form_hooks = fused_hook || unfused_hook || k3_hook || kg_hook || no_claim_hook;
+  f.tb = h->sym_counts && !h->per_bucket_products && !h->tb_block && !h->tb_failed && !Pd && want_grad && h->tb_Ls[0] &&
+         streams == 1 && (h->dtype == CB_F64 || h->dtype == CB_MIXED) &&
+         (tb_hook ? atoi(tb_hook) != 0 : (!form_hooks && B >= CB_TB_MIN_B));
+  if (f.tb && planned_now && h->tb.B != B) f.tb = false;
   {   // (tb_ew leaves one loss partial per half block of the upper block triangle in h->loss_part, B x tiles doubles)
-    const size_t nb16 = (size_t)LD / 16, cap = (size_t)B * ((LD + LG_TM - 1) / LG_TM) * ((LD + LG_TN - 1) / LG_TN);
-    if (nb16 * (nb16 + 1) > cap) use_tb = false;
+    const size_t nb16 = (size_t)LD / 16, cap = (size_t)B * tm * tn;
+    if (nb16 * (nb16 + 1) > cap) f.tb = false;
   }
-  // (the three bank kernels return at once when the planned solve in front of them stalled: EC_STALL)
-  const unsigned long long *skipw = planned_now ? h->ectl + (use_tb ? EC_SKIP : EC_STALL) : nullptr;
-  if (planned_now) {
-    TbTableArgs tbt;   // (the bank's spectral tables ride on the solve's last launch)
-    if (use_tb) tbt = TbTableArgs{h->tb.ns, h->tb.nd, h->tb.ng, h->tb_tf[h->tb_set], h->tb_tg[h->tb_set], h->F, h->E, h->H};
-    rc = enqueue_planned_solve(h, *plan, ++h->eseq, plan_first_slot, use_tb ? h->tb.rho_max : 0.0, tbt);
-  }
-  else if (!(reuse_eigh && h->have_prev)) rc = large_eigh(h, true);   // reuse: same matrix as the previous call (CB_REUSE_EIGH)
-  if (rc != CB_OK) return rc;
-  if (use_tb && !planned_now) {
-    double sg = 0.0;
-    HIP_TRY(hipMemcpyAsync(&sg, h->sigma, sizeof sg, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (!tb_in_range(h, B, 2.0 * sg)) {
-      rc = tb_rebuild(h, B, 2.0 * sg);
-      if (rc != CB_OK) return rc;
-      if (h->tb_failed) use_tb = false;
-    }
-  }
-  SlowScope scope_bank("large_eval: tables, bank, K4 enqueue");
-  if (!planned_now) mark(h, EV_EIGH);   // (a planned solve's last launch carries the mark)
-  const int tm = (LD + LG_TM - 1) / LG_TM, tn = (LD + LG_TN - 1) / LG_TN, tiles = tm * tn;
-  const double inv_n = normalize ? 1.0 / (h->comm ? h->n_global[0] : h->n_host[0]) : 1.0;
-  const int tiles_k1 = tn * (tn + 1) / 2;  // Pt is symmetric: upper-triangular tiles only
-  h->bank_tb = use_tb;
-  if (use_tb) {
-    // tables of the virtual buckets -> K1' (Psi_r of the forward skeleton, P_b of the long-branch buckets: ns + nd products
-    // into h->T) -> tb_ew (every element of every bucket: P_b, loss, G_b, the ng sums Gh_r into h->Gt) -> K2' (Th_r = Gh_r U
-    // over h->T) -> K3' (W_r = (Th_r^T U) o Phi(t_r) over h->Gt) -> the sum over r + the loss -> K4: the kernels of the per-bucket
-    // form on ns + nd and ng buckets instead of B.
-    const CbTimeBasisHost &bas = h->tb;
-    const int set = h->tb_set, nf = bas.ns + bas.nd, ng = bas.ng;
-    h->bank_fused = false;
-    h->bank_accum = false;
-    h->bank_kg = 1;
-    // (behind a planned solve the tables were written by its last launch, lge_finish: forward products 0.081 -> 0.076 ms, the
-    // solve +0.002)
-    if (!planned_now &&
-        cb_tb_launch_tables(LD, bas.ns, bas.nd, ng, h->tb_tf[set], h->tb_tg[set], h->lam, h->F, h->E, h->H, skipw, h->stream) != 0)
-      return fail(CB_EHIP, "tb_tables: launch failed");
-    // CB_MIXED: everything up to G_b in float64 (the forward products, P_b, the loss), Gh_r rounded to float32 once by tb_ew,
-    // the two gradient products on the float32 MFMA.  A mixed handle has no float64 Gt / T: Psi_r / P_b live (as doubles) in
-    // the float32 T buffer -- dead once tb_ew has run, before K2' writes Th_r there -- and need 2 (ns + nd) <= B of its planes.
-    const bool tb_mixed = h->dtype == CB_MIXED;
-    double *psi_buf = tb_mixed ? reinterpret_cast<double *>(h->T32) : h->T;
-    K1Args<double> k1{S, LD, nf, h->Vc, h->A, h->tb_tf[set], h->F, h->sigma, h->Ct, psi_buf, h->loss_part, inv_n, h->dsq, nullptr, skipw};
-    LAUNCH_STOP(stop_event(h, EV_K1), (k1_pt_loss_gt<double, double, false, 1, true>), dim3(tiles_k1 * nf), dim3(LG4_THREADS), 0, h->stream, k1);
-    const CbTbEwArgs ew{S, LD, B, bas.ns, bas.nd, ng, B - bas.nd, h->Ct, psi_buf, h->A, tb, h->tb_Ls[set], h->tb_Lg[set], h->Gt,
-                        tb_mixed ? h->Gt32 : nullptr, h->loss_part, inv_n, skipw};
-    int ew_parts = 0;
-    // (phase marks of a time-basis evaluation: CB_T_K1 = tables + forward products, CB_T_K2 = the elementwise kernel,
-    // CB_T_K3 = the two gradient products, CB_T_K4 = the sum over the virtual buckets + K4)
-    if (cb_tb_launch_ew(ew, h->stream, stop_event(h, EV_K2), &ew_parts) != 0) return fail(CB_EHIP, "tb_ew: launch failed");
-    const LossArgs la{h->loss_part, ew_parts, S, h->dsq, h->dirsum, inv_n, lossd, skipw};
-    const dim3 red_grid((unsigned)((LL + 255) / 256) + 1);
-    // (as ONE persistent launch -- k123_bank with an empty first stage, K3' tiles of a virtual bucket filling the drain of its
-    // K2' tiles -- the pair took 0.227 ms against 0.146 for the two launches: ~30 buckets are a short bank, EXPERIMENTS section 13;
-    // eight-wave tiles for the last product -- 450 tiles, fewer than two per CU -- measured: 0.1298 against 0.1306 ms, no gain)
-    if (tb_mixed) {
-      hipLaunchKernelGGL(lg_cast_f32, dim3((unsigned)((LL + 255) / 256)), dim3(256), 0, h->stream, LL, (size_t)0, h->U, h->Vc, h->A, h->F,
-                         h->Uf, h->Utf, h->Af, h->Ff);
-      K2Args<float> k2{LD, h->Gt32, h->Uf, h->T32, skipw};
-      K3Args<float> k3{LD, ng, h->T32, h->Uf, h->tb_tg[set], h->lam, h->E, h->H, h->Gt32, 1, skipw};
-      hipLaunchKernelGGL((k2_t_eq_g_u<float, 1>), dim3(tiles * ng), dim3(LG4_THREADS), 0, h->stream, k2);
-      LAUNCH_STOP(stop_event(h, EV_K3), (k3_w_phi<float, 1>), dim3(tiles_k1 * ng), dim3(LG4_THREADS), 0, h->stream, k3);
-      hipLaunchKernelGGL(k3_reduce_loss<float>, red_grid, dim3(256), 0, h->stream, h->Gt32, ng, LL, h->Mt, LD, la);
-    } else {
-      K2Args<double> k2{LD, h->Gt, h->U, h->T, skipw};
-      K3Args<double> k3{LD, ng, h->T, h->U, h->tb_tg[set], h->lam, h->E, h->H, h->Gt, 1, skipw};
-      hipLaunchKernelGGL((k2_t_eq_g_u<double, 1>), dim3(tiles * ng), dim3(LG4_THREADS), 0, h->stream, k2);
-      LAUNCH_STOP(stop_event(h, EV_K3), (k3_w_phi<double, 1>), dim3(tiles_k1 * ng), dim3(LG4_THREADS), 0, h->stream, k3);
-      hipLaunchKernelGGL(k3_reduce_loss<double>, red_grid, dim3(256), 0, h->stream, h->Gt, ng, LL, h->Mt, LD, la);
-    }
-    K4Args k4a{S, LD, h->Mt, h->Vc, h->X, nullptr, nullptr, nullptr};
-    k4a.skip = skipw;
-    launch_sg(h, k4a, 0);
-    K4Args k4b{S, LD, h->Vc, h->X, dQd, dA_padded ? nullptr : h->dsq, nullptr, nullptr};
-    k4b.skip = skipw;
-    launch_sg(h, k4b, 0, 0.0, 0.0, nullptr, stop_event(h, EV_K4));
-    HIP_TRY(hipGetLastError());
-    return CB_OK;
-  }
+  // Which form the three bank products take is decided by the SHAPE (live buckets; profiles/tools/r5_bank_sweep.py, round 5):
+  // the persistent launch k123_bank pays when the bank fills the chip several times over (its gain is the two drains it
+  // hides); a short bank -- the reference's real bank has 43 live buckets, one rank's share of an 8-rank job 17 -- is a chain
+  // of three tile latencies whatever is launched, and the persistent launch's 1024 resident workgroups (most of them waiting)
+  // make its tiles slower: 0.40 against 0.29 ms at 43 buckets, 0.24 against 0.14 at 17.  CB_BANK_UNFUSED=1 (per-kernel
+  // profiles, and the reference point of tests/test_gpu_s400_full.py) / CB_BANK_FUSED=1 force a form (test hooks).
+  f.fused = !Pd && want_grad && !unfused_hook && streams == 1 && h->bank_queue && (fused_hook || B >= CB_BANK_FUSED_MIN_B);
   // Symmetric counts: the buckets are summed BEFORE the last product (large_bank.hip.h, ky_reduce_loss / kphi_combine: one
   // streaming pass over T and 1 + CB_PHI_TERMS single products instead of a third product per bucket); CB_BANK_K3=1 keeps
   // the per-bucket third product (test hook: the reference point of the accuracy test).  Other banks: K3 on all tiles.
   // float64 banks only (with T_b in float32 the difference Le - Le^T amplifies its 1e-7 to 7e-3 in dL/dQ on the demo bank), and
   // from CB_BANK_SUM_FIRST_MIN_B live buckets on: the tail -- one pass over T, seven single products, the combination: ~45 us --
   // is dearer than the third product of a short bank (17 buckets: 0.160 against 0.153 ms); CB_BANK_K3=0 forces it on.
-  const char *k3_hook = cb_test_hook("CB_BANK_K3");
-  const bool accum = h->sym_counts && !h->per_bucket_products && !Pd && dQd != nullptr && h->Yk && n_parts == 1 && h->dtype == CB_F64 &&
-                     (k3_hook ? atoi(k3_hook) == 0 : (B >= CB_BANK_SUM_FIRST_MIN_B && h->phi_delta >= 4e-3));
   // (phi_delta = 0.2 / max t: a grid that reaches branch lengths beyond 50 -- the reference's ends at 13.7 -- would push the
   // quotient (Le_ij - Le_ji) / dlam down to eigenvalue distances where its cancellation costs more than six digits)
-  const int tiles_k3 = accum ? 0 : h->sym_counts ? tiles_k1 : tiles;
-  // M from the bucket sums: Y_k = sum_b T_b diag(c_bk) (+ the loss), Lt_k = Y_k^T U (one launch), M = combine(Lt, lam)
-  auto accumulated_tail = [&](bool narrow, hipEvent_t stop) {
-    const LossArgs la{h->loss_part, B * tiles_k1, S, h->dsq, h->dirsum, inv_n, lossd, skipw};
-    const dim3 red_grid((unsigned)((LL + 255) / 256) + 1);   // (+ the workgroup that sums the loss partials)
-    const YArgs ya{LD, B, tb, h->E, h->Yk};
-    if (narrow) hipLaunchKernelGGL(ky_reduce_loss<float>, red_grid, dim3(256), 0, h->stream, h->T32, ya, la);
-    else hipLaunchKernelGGL(ky_reduce_loss<double>, red_grid, dim3(256), 0, h->stream, h->T, ya, la);
-    K4Args gl{S, LD, h->Yk, h->U, h->Lk, nullptr, nullptr, nullptr};
-    gl.skip = skipw;
-    gl.ystride = LL;
-    launch_sg(h, gl, 0, 0.0, 0.0, nullptr, nullptr, 1 + CB_PHI_TERMS);
-    double delta = h->phi_delta;
-    if (const char *z = cb_test_hook("CB_PHI_Z")) delta *= atof(z) / 0.1;   // (experiment: the series' range |z| <= CB_PHI_Z)
-    LAUNCH_STOP(stop, kphi_combine<CB_PHI_TERMS>, dim3((unsigned)((LL + 255) / 256)), dim3(256), 0, h->stream, LD, h->Lk, h->lam, delta,
-                h->Mt, skipw);
-  };
-  // K1 -> K2 -> K3 as ONE persistent launch (k123_bank, large_bank.hip.h) whenever the gradient is wanted; CB_BANK_UNFUSED=1
-  // keeps the three launches (per-kernel profiles, and the reference point of tests/test_gpu_s400_full.py)
-  // (test hooks, read per call: the tests switch them inside one process)
-  const bool f32 = h->dtype == CB_F32 && !Pd, mixed = h->dtype == CB_MIXED && !Pd;
-  // Which form the three bank products take is decided by the SHAPE (live buckets; profiles/tools/r5_bank_sweep.py, round 5):
-  // the persistent launch k123_bank pays when the bank fills the chip several times over (its gain is the two drains it
-  // hides); a short bank -- the reference's real bank has 43 live buckets, one rank's share of an 8-rank job 17 -- is a chain
-  // of three tile latencies whatever is launched, and the persistent launch's 1024 resident workgroups (most of them waiting)
-  // make its tiles slower: 0.40 against 0.29 ms at 43 buckets, 0.24 against 0.14 at 17.  CB_BANK_UNFUSED=1 / CB_BANK_FUSED=1
-  // force a form (test hooks).
-  const bool unfused_env = cb_test_hook("CB_BANK_UNFUSED") != nullptr, fused_env = cb_test_hook("CB_BANK_FUSED") != nullptr;
-  const bool fused = !Pd && dQd && !unfused_env && n_parts == 1 && h->bank_queue && (fused_env || B >= CB_BANK_FUSED_MIN_B);
+  f.accum = h->sym_counts && !h->per_bucket_products && !Pd && want_grad && h->Yk && streams == 1 && h->dtype == CB_F64 &&
+            (k3_hook ? atoi(k3_hook) == 0 : (B >= CB_BANK_SUM_FIRST_MIN_B && h->phi_delta >= 4e-3));
+  f.tiles_k3 = f.accum ? 0 : h->sym_counts ? tn * (tn + 1) / 2 : tm * tn;
+  f.phi_delta = h->phi_delta;
+  if (phi_z_hook) f.phi_delta *= atof(phi_z_hook) / 0.1;   // (experiment: the series' range |z| <= CB_PHI_Z)
   // tile form of K1 .. K3 (large_bank.hip.h, lg4_gemm_tile): eight waves per 80 x 80 tile (two K-groups, two workgroups per
-  // CU) or four (four workgroups per CU); CB_BANK_KG=1 / 2 forces one (test hook).  cb_expm_bank keeps
-  // the four-wave form.
+  // CU) or four (four workgroups per CU); CB_BANK_KG=1 / 2 forces one (test hook).  cb_expm_bank keeps the four-wave form.
   // Below ~20 buckets every stage has at most two tiles per CU and the eight-wave tile's shorter latency wins (0.141 against
   // 0.152 ms at 17 buckets); above, four independent four-wave workgroups per CU overlap better than two eight-wave ones whose
   // K-groups share their barriers (0.75 against 0.65 ms at 129).  The float32 bank keeps the four-wave form: its P_b entries
   // of O(t^2) are sums with cancellation whose SIGN in float32 depends on the summation order (DESIGN / EXPERIMENTS, round 5).
-  int kg = (B < CB_BANK_KG2_MAX_B && !f32) ? 2 : 1;
-  if (const char *k = cb_test_hook("CB_BANK_KG")) kg = atoi(k) == 1 ? 1 : 2;
-  if (Pd) kg = 1;
-  h->bank_kg = kg;
-  h->bank_accum = accum;
-  // (queues and argument block: allocated with the handle, create_host.hip.h)
-  h->bank_fused = fused;
-  const dim3 tables_grid((unsigned)(((size_t)B * LD + 255) / 256));
-  if (!fused)
-    hipLaunchKernelGGL(lg_tables<NoBankArgs>, tables_grid, dim3(256), 0, h->stream, LD, B, tb, h->lam, h->sigma, h->F, h->E, h->H,
-                       NoBankArgs{}, (NoBankArgs *)nullptr, 0);
-  // float32 bank (cb_create(dtype = CB_F32)): the loss / gradient products run on the f32 MFMA from f32
-  // copies of this epoch's U, U^T, A and F; cb_expm_bank (Pd) always takes the float64 kernels
-  // CB_MIXED: P_b, the loss and G_b in float64 (the O(t^2) entries of P_b keep their relative accuracy),
-  // G_b rounded to float32 once, the two contractions on the float32 MFMA
-  if ((f32 || mixed) && !fused)
-    hipLaunchKernelGGL(lg_cast_f32, dim3((unsigned)((std::max(LL, (size_t)B * LD) + 255) / 256)), dim3(256), 0, h->stream, LL,
-                       (size_t)B * LD, h->U, h->Vc, h->A, h->F, h->Uf, h->Utf, h->Af, h->Ff);
-  // (no event between the spectral tables and K1: a hipEventRecord costs ~6 us of idle GPU between two kernels; CB_T_K1
-  // is the span from the end of the eigensolver to the end of K1 = lg_tables (4 us) [+ the float32 casts] + K1)
-  if (fused) {
-    // lg_tables (+ the argument block and the zeroed queues), then one launch of 4 workgroups per CU (fewer when the bank is
-    // small); the loss partials are summed after it
-    const int total = B * (tiles_k1 + tiles + tiles_k3), grid = std::min(h->bank_slots / kg, total);
-    const int sym = h->sym_counts ? 1 : 0;
-    const int test_no_claim = cb_test_hook("CB_BANK_TEST_NO_CLAIM") ? 1 : 0;   // (tests/test_gpu_s400_full.py: the help path)
-    // (the phase marks ride on the launches as stop events: handle_host.hip.h, stop_event())
-    if (h->profile && h->profile_now) h->ev_rec[EV_K1] = h->ev_rec[EV_K2] = false;   // CB_T_K1 = the whole launch (+ tables), see read_phase_times
-    const hipEvent_t bank_stop = stop_event(h, EV_K3);
-    auto launch = [&](auto args) {
-      typedef decltype(args) A;
-      A *dst = reinterpret_cast<A *>(h->bank_args);
-      hipLaunchKernelGGL(lg_tables<A>, tables_grid, dim3(256), 0, h->stream, LD, B, tb, h->lam, h->sigma, h->F, h->E, h->H, args, dst, grid);
-      return dst;
-    };
-    static_assert(sizeof(K123Args<float, float>) == sizeof(K123Args<double, double>) &&
-                  sizeof(K123Args<double, float>) == sizeof(K123Args<double, double>), "one argument block for all");
-    if (f32) {
-      // (the float32 casts read F: the tables first, then the casts, then the bank -- as in the separate launches)
-      K123Args<float, float> a{{S, LD, B, h->Utf, h->Af, tb, h->Ff, h->sigma, h->Ct32, h->Gt32, h->loss_part, inv_n, h->dsq, nullptr, skipw},
-                               {LD, h->Gt32, h->Uf, h->T32, skipw},
-                               {LD, B, h->T32, h->Uf, tb, h->lam, h->E, h->H, h->Gt32, sym, skipw},
-                               {h->bank_queue, B, tiles_k1, tiles, tiles_k3, h->bank_claims, test_no_claim}};
-      auto *dst = launch(a);
-      hipLaunchKernelGGL(lg_cast_f32, dim3((unsigned)((std::max(LL, (size_t)B * LD) + 255) / 256)), dim3(256), 0, h->stream, LL,
-                         (size_t)B * LD, h->U, h->Vc, h->A, h->F, h->Uf, h->Utf, h->Af, h->Ff);
-      if (cb_launch_bank_fused(1, kg, dst, grid, h->stream, bank_stop) != 0) return fail(CB_EHIP, "k123_bank: launch failed");
-    } else if (mixed) {
-      K123Args<double, float> a{{S, LD, B, h->Vc, h->A, tb, h->F, h->sigma, h->Ct, h->Gt32, h->loss_part, inv_n, h->dsq, nullptr, skipw},
-                                {LD, h->Gt32, h->Uf, h->T32, skipw},
-                                {LD, B, h->T32, h->Uf, tb, h->lam, h->E, h->H, h->Gt32, sym, skipw},
-                                {h->bank_queue, B, tiles_k1, tiles, tiles_k3, h->bank_claims, test_no_claim}};
-      auto *dst = launch(a);
-      hipLaunchKernelGGL(lg_cast_f32, dim3((unsigned)((std::max(LL, (size_t)B * LD) + 255) / 256)), dim3(256), 0, h->stream, LL,
-                         (size_t)B * LD, h->U, h->Vc, h->A, h->F, h->Uf, h->Utf, h->Af, h->Ff);
-      if (cb_launch_bank_fused(2, kg, dst, grid, h->stream, bank_stop) != 0) return fail(CB_EHIP, "k123_bank: launch failed");
-    } else {
-      K123Args<double, double> a{{S, LD, B, h->Vc, h->A, tb, h->F, h->sigma, h->Ct, h->Gt, h->loss_part, inv_n, h->dsq, nullptr, skipw},
-                                 {LD, h->Gt, h->U, h->T, skipw},
-                                 {LD, B, h->T, h->U, tb, h->lam, h->E, h->H, h->Gt, sym, skipw},
-                                 {h->bank_queue, B, tiles_k1, tiles, tiles_k3, h->bank_claims, test_no_claim}};
-      auto *dst = launch(a);
-      if (cb_launch_bank_fused(0, kg, dst, grid, h->stream, bank_stop) != 0) return fail(CB_EHIP, "k123_bank: launch failed");
-    }
-    const LossArgs la{h->loss_part, B * tiles_k1, S, h->dsq, h->dirsum, inv_n, lossd, skipw};
-    const dim3 red_grid((unsigned)((LL + 255) / 256) + 1);   // (+ the workgroup that sums the loss partials)
-    if (accum)
-      accumulated_tail(f32 || mixed, nullptr);
-    else if (f32 || mixed)
-      hipLaunchKernelGGL(k3_reduce_loss<float>, red_grid, dim3(256), 0, h->stream, h->Gt32, B, LL, h->Mt, h->sym_counts ? LD : 0, la);
-    else
-      hipLaunchKernelGGL(k3_reduce_loss<double>, red_grid, dim3(256), 0, h->stream, h->Gt, B, LL, h->Mt, h->sym_counts ? LD : 0, la);
-    // (a stalled planned solve: the reduction and K4 return at once too -- nothing runs on stale Gt / T, and h->loss / h->Mt
-    // are only written by the evaluation that follows a finished solve)
-    K4Args k4a{S, LD, h->Mt, h->Vc, h->X, nullptr, nullptr, nullptr};
-    k4a.skip = skipw;
-    launch_sg(h, k4a, 0);
-    K4Args k4b{S, LD, h->Vc, h->X, dQd, dA_padded ? nullptr : h->dsq, nullptr, nullptr};
-    k4b.skip = skipw;
-    launch_sg(h, k4b, 0, 0.0, 0.0, nullptr, stop_event(h, EV_K4));
-    HIP_TRY(hipGetLastError());
-    return CB_OK;
-  }
-  // (the separate launches in the tile form `kg`: same bits as the fused launch of that form)
-  // (the phase marks ride on the kernels as stop events -- a hipEventRecord between two kernels costs ~5 us of idle GPU)
-#define LAUNCH_KG_ON(st_, ev_, kern1, kern2, grid_, args_)                                                     \
-  do {                                                                                                         \
-    if (kg == 2) LAUNCH_STOP(ev_, kern2, grid_, dim3(2 * LG4_THREADS), 0, st_, args_);                         \
-    else LAUNCH_STOP(ev_, kern1, grid_, dim3(LG4_THREADS), 0, st_, args_);                                     \
-  } while (0)
-#define LAUNCH_KG(ev_, kern1, kern2, grid_, args_) LAUNCH_KG_ON(h->stream, ev_, kern1, kern2, grid_, args_)
-  const hipEvent_t ev_k1 = stop_event(h, EV_K1);   // (null when the call is not profiled)
-  if (f32) {
-    K1Args<float> k1{S, LD, B, h->Utf, h->Af, tb, h->Ff, h->sigma, h->Ct32, h->Gt32, h->loss_part, inv_n, h->dsq, nullptr, skipw};
-    LAUNCH_KG(ev_k1, (k1_pt_loss_gt<float, float, false, 1>), (k1_pt_loss_gt<float, float, false, 2>), dim3(tiles_k1 * B), k1);
-  } else if (mixed) {
-    K1Args<double, float> k1{S, LD, B, h->Vc, h->A, tb, h->F, h->sigma, h->Ct, h->Gt32, h->loss_part, inv_n, h->dsq, nullptr, skipw};
-    LAUNCH_KG(ev_k1, (k1_pt_loss_gt<double, float, false, 1>), (k1_pt_loss_gt<double, float, false, 2>), dim3(tiles_k1 * B), k1);
-  } else if (n_parts > 1 && !Pd && dQd && B >= 4 * n_parts && !h->comm && !h->profile) {
-    // OPT-IN (CB_BANK_STREAMS=n, float64 bank, no profile markers): the buckets in n equal parts on n queues,
-    // K1 -> K2 -> K3 each, so that the drain of one part's kernel overlaps the other parts' kernels; same results bit
-    // for bit (disjoint buckets, the bucket sum is taken after the join).  n = 2: 1.110 -> 1.072 ms per epoch on the
-    // bench bank; 3 and 4 are slower again.  Not the default: with kernels of two queues sharing the chip the
-    // per-kernel durations the bench reports (HIP events on one stream, rocprof averages) stop meaning anything.
-    if (!h->ev_fork) HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    for (int p = 1; p < n_parts; ++p)
-      if (!h->xstream[p - 1]) {
-        HIP_TRY(hipStreamCreateWithFlags(&h->xstream[p - 1], hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&h->ev_join[p - 1], hipEventDisableTiming));
-      }
-    HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
-    for (int p = 1; p < n_parts; ++p) HIP_TRY(hipStreamWaitEvent(h->xstream[p - 1], h->ev_fork, 0));
-    auto part_of = [&](int p, int &b0, int &Bs, hipStream_t &st) {
-      b0 = (int)((long)B * p / n_parts);
-      Bs = (int)((long)B * (p + 1) / n_parts) - b0;
-      st = p ? h->xstream[p - 1] : h->stream;
-    };
-    for (int p = 0; p < n_parts; ++p) {
-      int b0, Bs; hipStream_t st;
-      part_of(p, b0, Bs, st);
-      K1Args<double> k1{S, LD, Bs, h->Vc, h->A, tb + b0, h->F + (size_t)b0 * LD, h->sigma, h->Ct + b0 * LL, h->Gt + b0 * LL,
-                        h->loss_part + (size_t)b0 * tiles_k1, inv_n, h->dsq, nullptr};
-      LAUNCH_KG_ON(st, nullptr, (k1_pt_loss_gt<double, double, false, 1>), (k1_pt_loss_gt<double, double, false, 2>), dim3(tiles_k1 * Bs), k1);
-    }
-    for (int p = 0; p < n_parts; ++p) {
-      int b0, Bs; hipStream_t st;
-      part_of(p, b0, Bs, st);
-      K2Args<double> k2{LD, h->Gt + b0 * LL, h->U, h->T + b0 * LL};
-      LAUNCH_KG_ON(st, nullptr, (k2_t_eq_g_u<double, 1>), (k2_t_eq_g_u<double, 2>), dim3(tiles * Bs), k2);
-    }
-    for (int p = 0; p < n_parts; ++p) {
-      int b0, Bs; hipStream_t st;
-      part_of(p, b0, Bs, st);
-      K3Args<double> k3{LD, Bs, h->T + b0 * LL, h->U, tb + b0, h->lam, h->E + (size_t)b0 * LD, h->H + (size_t)b0 * LD,
-                        h->Gt + b0 * LL, h->sym_counts ? 1 : 0};
-      LAUNCH_KG_ON(st, nullptr, (k3_w_phi<double, 1>), (k3_w_phi<double, 2>), dim3(tiles_k3 * Bs), k3);
-    }
-    for (int p = 1; p < n_parts; ++p) {
-      HIP_TRY(hipEventRecord(h->ev_join[p - 1], h->xstream[p - 1]));
-      HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join[p - 1], 0));
-    }
-    hipLaunchKernelGGL(lg_finish_loss, dim3(1), dim3(256), 0, h->stream, h->loss_part, B * tiles_k1, S,
-                       h->dsq, h->dirsum, inv_n, lossd);
-    hipLaunchKernelGGL(k3_reduce<double>, dim3((unsigned)((LL + 255) / 256)), dim3(256), 0, h->stream,
-                       h->Gt, B, LL, h->Mt, h->sym_counts ? LD : 0);
-    K4Args k4a{S, LD, h->Mt, h->Vc, h->X, nullptr, nullptr, nullptr};
-    launch_sg(h, k4a, 0);
-    K4Args k4b{S, LD, h->Vc, h->X, dQd, dA_padded ? nullptr : h->dsq, nullptr, nullptr};
-    launch_sg(h, k4b, 0);
-    HIP_TRY(hipGetLastError());
-    return CB_OK;
+  f.kg = (B < CB_BANK_KG2_MAX_B && !f32) ? 2 : 1;
+  if (kg_hook) f.kg = atoi(kg_hook) == 1 ? 1 : 2;
+  if (Pd) f.kg = 1;
+  // (the parts need four buckets each; a sharded rank's all-reduce and the profile markers live on the handle's one stream)
+  if (streams > 1 && h->dtype == CB_F64 && !Pd && want_grad && B >= 4 * streams && !h->comm && !h->profile) f.n_parts = streams;
+  f.test_no_claim = no_claim_hook ? 1 : 0;
+  return f;
+}
+
+// The operands of one evaluation, shared by the enqueue functions of every form.
+struct LargeCall {
+  int B;                             // buckets (the loss visits live buckets only) and their branch lengths t
+  const double *t;
+  double inv_n;
+  double *loss, *dQ, *Pd;            // dQ null: the loss alone; Pd: cb_expm_bank's P_b instead of the loss
+  bool dA_padded, planned_now;       // dQ receives dL/dA as a padded LD x LD matrix; the solve in front is a plan
+  const unsigned long long *skipw;   // behind a planned solve: the word that makes the bank kernels return at once
+  size_t LL;
+  int tiles, tiles_k1;               // per bucket: the full tile grid, its upper triangle (Pt is symmetric)
+};
+
+// The buffers of the three number formats (element types T1 of K1's operands, TG of the gradient products):
+// float64 (double, double); CB_F32 (float, float): the loss / gradient products on the f32 MFMA from float32 copies of this
+// epoch's U^T, A and F; CB_MIXED (double, float): P_b, the loss and G_b in float64 (the O(t^2) entries of P_b keep their relative
+// accuracy), G_b rounded to float32 once, the two contractions on the float32 MFMA.  cb_expm_bank always takes float64.
+template <typename T1, typename TG>
+struct BankBufs {
+  const T1 *Ut, *A, *F, *Ct;   // K1's operands
+  TG *Gt, *T;                  // G_b^T (then W_b), T_b
+  const TG *U;
+  int variant;                 // cb_launch_bank_fused
+};
+template <typename T1, typename TG>
+static BankBufs<T1, TG> bank_bufs(const cb_bank *h) {
+  if constexpr (std::is_same_v<T1, float>) return {h->Utf, h->Af, h->Ff, h->Ct32, h->Gt32, h->T32, h->Uf, 1};
+  else if constexpr (std::is_same_v<TG, float>) return {h->Vc, h->A, h->F, h->Ct, h->Gt32, h->T32, h->Uf, 2};
+  else return {h->Vc, h->A, h->F, h->Ct, h->Gt, h->T, h->U, 0};
+}
+// calls fn(T1{}, TG{}) with the element types of the handle's number format
+template <typename Fn>
+static int with_format(const cb_bank *h, bool Pd, Fn &&fn) {
+  if (!Pd && h->dtype == CB_F32) return fn(float{}, float{});
+  if (!Pd && h->dtype == CB_MIXED) return fn(double{}, float{});
+  return fn(double{}, double{});
+}
+
+// a tile kernel of K1 .. K3 in the tile form kg (its four-wave and eight-wave instantiations); `ev`: the phase mark it carries
+// as its stop event (a hipEventRecord between two kernels costs ~5 us of idle GPU)
+template <typename Args>
+static void launch_kg(int kg, void (*kern1)(Args), void (*kern2)(Args), dim3 grid, hipStream_t st, hipEvent_t ev, const Args &a) {
+  if (kg == 2) LAUNCH_STOP(ev, kern2, grid, dim3(2 * LG4_THREADS), 0, st, a);
+  else LAUNCH_STOP(ev, kern1, grid, dim3(LG4_THREADS), 0, st, a);
+}
+// float32 copies of U, U^T, A and F (the first nF entries; they read F: behind the tables)
+static void launch_cast_f32(cb_bank *h, const LargeCall &c, size_t nF) {
+  hipLaunchKernelGGL(lg_cast_f32, dim3((unsigned)((std::max(c.LL, nF) + 255) / 256)), dim3(256), 0, h->stream, c.LL, nF, h->U,
+                     h->Vc, h->A, h->F, h->Uf, h->Utf, h->Af, h->Ff);
+}
+static void launch_tables(cb_bank *h, const LargeCall &c) {   // spectral tables F, E, H of the buckets
+  hipLaunchKernelGGL(lg_tables<NoBankArgs>, dim3((unsigned)(((size_t)c.B * h->LD + 255) / 256)), dim3(256), 0, h->stream, h->LD,
+                     c.B, c.t, h->lam, h->sigma, h->F, h->E, h->H, NoBankArgs{}, (NoBankArgs *)nullptr, 0);
+}
+
+// K4: dQ = D^1/2 (U M U^T) D^-1/2 (or dL/dA, padded) from M = h->Mt, in two single products
+static void enqueue_k4(cb_bank *h, const LargeCall &c, const unsigned long long *skip, hipEvent_t stop) {
+  const int S = h->S, LD = h->LD;
+  K4Args k4a{S, LD, h->Mt, h->Vc, h->X, nullptr, nullptr, nullptr};
+  k4a.skip = skip;
+  launch_sg(h, k4a, 0);
+  K4Args k4b{S, LD, h->Vc, h->X, c.dQ, c.dA_padded ? nullptr : h->dsq, nullptr, nullptr};
+  k4b.skip = skip;
+  launch_sg(h, k4b, 0, 0.0, 0.0, nullptr, stop);
+}
+
+// The tail of every form but CB_BANK_STREAMS: M from the bank's output + the loss from `nparts` partials, then K4.
+// Per-bucket products: M = the sum over the `nb` products W_b of `src` (sym_ld = LD: only their upper triangles were written).
+// `accum`: src = T_b; M from the bucket sums Y_k = sum_b T_b diag(c_bk) (+ the loss), Lt_k = Y_k^T U (one launch),
+// M = combine(Lt, lam); `k3_stop` rides on the combination.
+// (a stalled planned solve: the reduction and K4 return at once too -- nothing runs on stale Gt / T, and h->loss / h->Mt are
+// only written by the evaluation that follows a finished solve)
+template <typename TG>
+static int enqueue_tail(cb_bank *h, const LargeBankForm &f, const LargeCall &c, const TG *src, int nb, int nparts, int sym_ld,
+                        hipEvent_t k3_stop) {
+  const int LD = h->LD;
+  const LossArgs la{h->loss_part, nparts, h->S, h->dsq, h->dirsum, c.inv_n, c.loss, c.skipw};
+  const dim3 red_grid((unsigned)((c.LL + 255) / 256) + 1);   // (+ the workgroup that sums the loss partials)
+  if (f.accum) {
+    hipLaunchKernelGGL(ky_reduce_loss<TG>, red_grid, dim3(256), 0, h->stream, src, YArgs{LD, c.B, c.t, h->E, h->Yk}, la);
+    K4Args gl{h->S, LD, h->Yk, h->U, h->Lk, nullptr, nullptr, nullptr};
+    gl.skip = c.skipw;
+    gl.ystride = c.LL;
+    launch_sg(h, gl, 0, 0.0, 0.0, nullptr, nullptr, 1 + CB_PHI_TERMS);
+    LAUNCH_STOP(k3_stop, kphi_combine<CB_PHI_TERMS>, dim3((unsigned)((c.LL + 255) / 256)), dim3(256), 0, h->stream, LD, h->Lk,
+                h->lam, f.phi_delta, h->Mt, c.skipw);
   } else {
-    K1Args<double> k1{S, LD, B, h->Vc, h->A, tb, h->F, h->sigma, h->Ct, h->Gt, h->loss_part, inv_n, h->dsq, Pd, skipw};
-    if (Pd) LAUNCH_STOP(ev_k1, (k1_pt_loss_gt<double, double, true>), dim3(tiles_k1 * B), dim3(LG4_THREADS), 0, h->stream, k1);
-    else LAUNCH_KG(ev_k1, (k1_pt_loss_gt<double, double, false, 1>), (k1_pt_loss_gt<double, double, false, 2>), dim3(tiles_k1 * B), k1);
+    hipLaunchKernelGGL(k3_reduce_loss<TG>, red_grid, dim3(256), 0, h->stream, src, nb, c.LL, h->Mt, sym_ld, la);
   }
-  if (Pd) {
-    HIP_TRY(hipGetLastError());
-    return CB_OK;
-  }
-  if (!dQd) {   // the loss alone
-    hipLaunchKernelGGL(lg_finish_loss, dim3(1), dim3(256), 0, h->stream, h->loss_part, B * tiles_k1, S,
-                       h->dsq, h->dirsum, inv_n, lossd);
-    HIP_TRY(hipGetLastError());
-    return CB_OK;
-  }
-  // K1 -> K2 -> K3 back to back (the loss partials are summed beside the bucket sum, behind K3: a one-workgroup launch between
-  // K1 and K2 would sit on the chain), then the bucket sum + loss, then K4 -- the sequence of the fused path as three launches
-  const LossArgs la{h->loss_part, B * tiles_k1, S, h->dsq, h->dirsum, inv_n, lossd, skipw};
-  const dim3 red_grid((unsigned)((LL + 255) / 256) + 1);   // (+ the workgroup that sums the loss partials)
-  if (f32 || mixed) {
-    K2Args<float> k2{LD, h->Gt32, h->Uf, h->T32, skipw};
-    LAUNCH_KG(stop_event(h, EV_K2), (k2_t_eq_g_u<float, 1>), (k2_t_eq_g_u<float, 2>), dim3(tiles * B), k2);
-    if (accum) {
-      accumulated_tail(true, stop_event(h, EV_K3));   // (CB_T_K3: the bucket sums, their products and the combination)
-    } else {
-      K3Args<float> k3{LD, B, h->T32, h->Uf, tb, h->lam, h->E, h->H, h->Gt32, h->sym_counts ? 1 : 0, skipw};
-      LAUNCH_KG(stop_event(h, EV_K3), (k3_w_phi<float, 1>), (k3_w_phi<float, 2>), dim3(tiles_k3 * B), k3);
-      hipLaunchKernelGGL(k3_reduce_loss<float>, red_grid, dim3(256), 0, h->stream, h->Gt32, B, LL, h->Mt, h->sym_counts ? LD : 0, la);
-    }
-  } else {
-    K2Args<double> k2{LD, h->Gt, h->U, h->T, skipw};
-    LAUNCH_KG(stop_event(h, EV_K2), (k2_t_eq_g_u<double, 1>), (k2_t_eq_g_u<double, 2>), dim3(tiles * B), k2);
-    if (accum) {
-      accumulated_tail(false, stop_event(h, EV_K3));
-    } else {
-      K3Args<double> k3{LD, B, h->T, h->U, tb, h->lam, h->E, h->H, h->Gt, h->sym_counts ? 1 : 0, skipw};
-      LAUNCH_KG(stop_event(h, EV_K3), (k3_w_phi<double, 1>), (k3_w_phi<double, 2>), dim3(tiles_k3 * B), k3);
-      hipLaunchKernelGGL(k3_reduce_loss<double>, red_grid, dim3(256), 0, h->stream, h->Gt, B, LL, h->Mt, h->sym_counts ? LD : 0, la);
-    }
-  }
-  {
-    K4Args k4a{S, LD, h->Mt, h->Vc, h->X, nullptr, nullptr, nullptr};
-    k4a.skip = skipw;
-    launch_sg(h, k4a, 0);
-    K4Args k4b{S, LD, h->Vc, h->X, dQd, dA_padded ? nullptr : h->dsq, nullptr, nullptr};
-    k4b.skip = skipw;
-    launch_sg(h, k4b, 0, 0.0, 0.0, nullptr, stop_event(h, EV_K4));
-  }
-#undef LAUNCH_KG
-#undef LAUNCH_KG_ON
+  enqueue_k4(h, c, c.skipw, stop_event(h, EV_K4));
   HIP_TRY(hipGetLastError());
   return CB_OK;
+}
+
+// The time basis: tables of the virtual buckets -> K1' (Psi_r of the forward skeleton, P_b of the long-branch buckets: ns + nd
+// products into h->T) -> tb_ew (every element of every bucket: P_b, loss, G_b, the ng sums Gh_r into h->Gt) -> K2' (Th_r = Gh_r U
+// over h->T) -> K3' (W_r = (Th_r^T U) o Phi(t_r) over h->Gt) -> the sum over r + the loss -> K4: the kernels of the per-bucket
+// form on ns + nd and ng buckets instead of B.  TG = float: CB_MIXED -- everything up to G_b in float64 (the forward products,
+// P_b, the loss), Gh_r rounded to float32 once by tb_ew, the two gradient products on the float32 MFMA.  A mixed handle has no
+// float64 Gt / T: Psi_r / P_b live (as doubles) in the float32 T buffer -- dead once tb_ew has run, before K2' writes Th_r
+// there -- and need 2 (ns + nd) <= B of its planes.
+// (phase marks: CB_T_K1 = tables + forward products, CB_T_K2 = the elementwise kernel, CB_T_K3 = the two gradient products,
+// CB_T_K4 = the sum over the virtual buckets + K4)
+template <typename TG>
+static int enqueue_tb_bank(cb_bank *h, const LargeBankForm &f, const LargeCall &c) {
+  constexpr bool mixed = std::is_same_v<TG, float>;
+  const CbTimeBasisHost &bas = h->tb;
+  const int S = h->S, LD = h->LD, set = h->tb_set, nf = bas.ns + bas.nd, ng = bas.ng;
+  const auto bb = bank_bufs<double, TG>(h);
+  // (behind a planned solve the tables were written by its last launch, lge_finish: forward products 0.081 -> 0.076 ms, the
+  // solve +0.002)
+  if (!c.planned_now && cb_tb_launch_tables(LD, bas.ns, bas.nd, ng, h->tb_tf[set], h->tb_tg[set], h->lam, h->F, h->E, h->H,
+                                            c.skipw, h->stream) != 0)
+    return fail(CB_EHIP, "tb_tables: launch failed");
+  double *psi_buf = mixed ? reinterpret_cast<double *>(h->T32) : h->T;
+  K1Args<double> k1{S, LD, nf, h->Vc, h->A, h->tb_tf[set], h->F, h->sigma, h->Ct, psi_buf, h->loss_part, c.inv_n, h->dsq, nullptr, c.skipw};
+  LAUNCH_STOP(stop_event(h, EV_K1), (k1_pt_loss_gt<double, double, false, 1, true>), dim3(c.tiles_k1 * nf), dim3(LG4_THREADS), 0,
+              h->stream, k1);
+  const CbTbEwArgs ew{S, LD, c.B, bas.ns, bas.nd, ng, c.B - bas.nd, h->Ct, psi_buf, h->A, c.t, h->tb_Ls[set], h->tb_Lg[set], h->Gt,
+                      mixed ? h->Gt32 : nullptr, h->loss_part, c.inv_n, c.skipw};
+  int ew_parts = 0;
+  if (cb_tb_launch_ew(ew, h->stream, stop_event(h, EV_K2), &ew_parts) != 0) return fail(CB_EHIP, "tb_ew: launch failed");
+  // (as ONE persistent launch -- k123_bank with an empty first stage, K3' tiles of a virtual bucket filling the drain of its
+  // K2' tiles -- the pair took 0.227 ms against 0.146 for the two launches: ~30 buckets are a short bank, EXPERIMENTS section 13;
+  // eight-wave tiles for the last product -- 450 tiles, fewer than two per CU -- measured: 0.1298 against 0.1306 ms, no gain)
+  if (mixed) launch_cast_f32(h, c, 0);
+  const K2Args<TG> k2{LD, bb.Gt, bb.U, bb.T, c.skipw};
+  const K3Args<TG> k3{LD, ng, bb.T, bb.U, h->tb_tg[set], h->lam, h->E, h->H, bb.Gt, 1, c.skipw};
+  hipLaunchKernelGGL((k2_t_eq_g_u<TG, 1>), dim3(c.tiles * ng), dim3(LG4_THREADS), 0, h->stream, k2);
+  LAUNCH_STOP(stop_event(h, EV_K3), (k3_w_phi<TG, 1>), dim3(c.tiles_k1 * ng), dim3(LG4_THREADS), 0, h->stream, k3);
+  return enqueue_tail<TG>(h, f, c, bb.Gt, ng, ew_parts, LD, nullptr);
+}
+
+// K1 -> K2 -> K3 as ONE persistent launch (k123_bank, large_bank.hip.h): lg_tables (+ the argument block and the zeroed queues),
+// then one launch of 4 workgroups per CU (fewer when the bank is small); the loss partials are summed after it.
+template <typename T1, typename TG>
+static int enqueue_fused_bank(cb_bank *h, const LargeBankForm &f, const LargeCall &c) {
+  const int S = h->S, LD = h->LD, B = c.B;
+  const auto bb = bank_bufs<T1, TG>(h);
+  const int total = B * (c.tiles_k1 + c.tiles + f.tiles_k3), grid = std::min(h->bank_slots / f.kg, total);
+  const int sym = h->sym_counts ? 1 : 0;
+  // (the phase marks ride on the launches as stop events: handle_host.hip.h, stop_event())
+  if (h->profile && h->profile_now) h->ev_rec[EV_K1] = h->ev_rec[EV_K2] = false;   // CB_T_K1 = the whole launch (+ tables), see read_phase_times
+  const hipEvent_t bank_stop = stop_event(h, EV_K3);
+  static_assert(sizeof(K123Args<float, float>) == sizeof(K123Args<double, double>) &&
+                sizeof(K123Args<double, float>) == sizeof(K123Args<double, double>), "one argument block for all");
+  const K123Args<T1, TG> a{{S, LD, B, bb.Ut, bb.A, c.t, bb.F, h->sigma, bb.Ct, bb.Gt, h->loss_part, c.inv_n, h->dsq, nullptr, c.skipw},
+                           {LD, bb.Gt, bb.U, bb.T, c.skipw},
+                           {LD, B, bb.T, bb.U, c.t, h->lam, h->E, h->H, bb.Gt, sym, c.skipw},
+                           {h->bank_queue, B, c.tiles_k1, c.tiles, f.tiles_k3, h->bank_claims, f.test_no_claim}};
+  auto *dst = reinterpret_cast<K123Args<T1, TG> *>(h->bank_args);
+  hipLaunchKernelGGL((lg_tables<K123Args<T1, TG>>), dim3((unsigned)(((size_t)B * LD + 255) / 256)), dim3(256), 0, h->stream, LD, B,
+                     c.t, h->lam, h->sigma, h->F, h->E, h->H, a, dst, grid);
+  // (the float32 casts read F: the tables first, then the casts, then the bank -- as in the separate launches)
+  if (std::is_same_v<TG, float>) launch_cast_f32(h, c, (size_t)B * LD);
+  if (cb_launch_bank_fused(bb.variant, f.kg, dst, grid, h->stream, bank_stop) != 0) return fail(CB_EHIP, "k123_bank: launch failed");
+  return enqueue_tail<TG>(h, f, c, f.accum ? bb.T : bb.Gt, B, B * c.tiles_k1, h->sym_counts ? LD : 0, nullptr);
+}
+
+// The separate launches in the tile form kg (same bits as the fused launch of that form): K1 -> K2 -> K3 back to back (the loss
+// partials are summed beside the bucket sum, behind K3: a one-workgroup launch between K1 and K2 would sit on the chain), then
+// the bucket sum + loss, then K4 -- the sequence of the fused path as three launches.  Also the loss alone (c.dQ null) and
+// cb_expm_bank's P_b (c.Pd).
+// (no event between the spectral tables and K1: a hipEventRecord costs ~6 us of idle GPU between two kernels; CB_T_K1
+// is the span from the end of the eigensolver to the end of K1 = lg_tables (4 us) [+ the float32 casts] + K1)
+template <typename T1, typename TG>
+static int enqueue_split_bank(cb_bank *h, const LargeBankForm &f, const LargeCall &c) {
+  const int S = h->S, LD = h->LD, B = c.B;
+  const auto bb = bank_bufs<T1, TG>(h);
+  launch_tables(h, c);
+  if (std::is_same_v<TG, float>) launch_cast_f32(h, c, (size_t)B * LD);
+  const K1Args<T1, TG> k1{S, LD, B, bb.Ut, bb.A, c.t, bb.F, h->sigma, bb.Ct, bb.Gt, h->loss_part, c.inv_n, h->dsq, c.Pd, c.skipw};
+  const hipEvent_t ev_k1 = stop_event(h, EV_K1);   // (null when the call is not profiled)
+  if constexpr (std::is_same_v<TG, double>) {
+    if (c.Pd) {
+      LAUNCH_STOP(ev_k1, (k1_pt_loss_gt<double, double, true>), dim3(c.tiles_k1 * B), dim3(LG4_THREADS), 0, h->stream, k1);
+      HIP_TRY(hipGetLastError());
+      return CB_OK;
+    }
+  }
+  launch_kg(f.kg, k1_pt_loss_gt<T1, TG, false, 1>, k1_pt_loss_gt<T1, TG, false, 2>, dim3(c.tiles_k1 * B), h->stream, ev_k1, k1);
+  if (!c.dQ) {   // the loss alone
+    hipLaunchKernelGGL(lg_finish_loss, dim3(1), dim3(256), 0, h->stream, h->loss_part, B * c.tiles_k1, S, h->dsq, h->dirsum,
+                       c.inv_n, c.loss);
+    HIP_TRY(hipGetLastError());
+    return CB_OK;
+  }
+  const K2Args<TG> k2{LD, bb.Gt, bb.U, bb.T, c.skipw};
+  launch_kg(f.kg, k2_t_eq_g_u<TG, 1>, k2_t_eq_g_u<TG, 2>, dim3(c.tiles * B), h->stream, stop_event(h, EV_K2), k2);
+  const hipEvent_t ev_k3 = stop_event(h, EV_K3);   // (CB_T_K3: K3, or the bucket sums, their products and the combination)
+  if (f.accum) return enqueue_tail<TG>(h, f, c, bb.T, B, B * c.tiles_k1, 0, ev_k3);
+  const K3Args<TG> k3{LD, B, bb.T, bb.U, c.t, h->lam, h->E, h->H, bb.Gt, h->sym_counts ? 1 : 0, c.skipw};
+  launch_kg(f.kg, k3_w_phi<TG, 1>, k3_w_phi<TG, 2>, dim3(f.tiles_k3 * B), h->stream, ev_k3, k3);
+  return enqueue_tail<TG>(h, f, c, bb.Gt, B, B * c.tiles_k1, h->sym_counts ? LD : 0, nullptr);
+}
+
+// CB_BANK_STREAMS (float64, see choose_large_form): the separate launches of the buckets in f.n_parts parts on as many queues
+static int enqueue_stream_split_bank(cb_bank *h, const LargeBankForm &f, const LargeCall &c) {
+  const int S = h->S, LD = h->LD, B = c.B, n = f.n_parts;
+  const size_t LL = c.LL;
+  launch_tables(h, c);
+  if (!h->ev_fork) HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+  for (int p = 1; p < n; ++p)
+    if (!h->xstream[p - 1]) {
+      HIP_TRY(hipStreamCreateWithFlags(&h->xstream[p - 1], hipStreamNonBlocking));
+      HIP_TRY(hipEventCreateWithFlags(&h->ev_join[p - 1], hipEventDisableTiming));
+    }
+  HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
+  for (int p = 1; p < n; ++p) HIP_TRY(hipStreamWaitEvent(h->xstream[p - 1], h->ev_fork, 0));
+  for (int k = 1; k <= 3; ++k)   // K1 of every part, then K2 of every part, then K3
+    for (int p = 0; p < n; ++p) {
+      const int b0 = (int)((long)B * p / n), Bs = (int)((long)B * (p + 1) / n) - b0;
+      const hipStream_t st = p ? h->xstream[p - 1] : h->stream;
+      double *Gt = h->Gt + b0 * LL, *T = h->T + b0 * LL;
+      if (k == 1) {
+        K1Args<double> k1{S, LD, Bs, h->Vc, h->A, c.t + b0, h->F + (size_t)b0 * LD, h->sigma, h->Ct + b0 * LL, Gt,
+                          h->loss_part + (size_t)b0 * c.tiles_k1, c.inv_n, h->dsq, nullptr};
+        launch_kg(f.kg, k1_pt_loss_gt<double, double, false, 1>, k1_pt_loss_gt<double, double, false, 2>, dim3(c.tiles_k1 * Bs),
+                  st, nullptr, k1);
+      } else if (k == 2) {
+        launch_kg(f.kg, k2_t_eq_g_u<double, 1>, k2_t_eq_g_u<double, 2>, dim3(c.tiles * Bs), st, nullptr, K2Args<double>{LD, Gt, h->U, T});
+      } else {
+        K3Args<double> k3{LD, Bs, T, h->U, c.t + b0, h->lam, h->E + (size_t)b0 * LD, h->H + (size_t)b0 * LD, Gt, h->sym_counts ? 1 : 0};
+        launch_kg(f.kg, k3_w_phi<double, 1>, k3_w_phi<double, 2>, dim3(f.tiles_k3 * Bs), st, nullptr, k3);
+      }
+    }
+  for (int p = 1; p < n; ++p) {
+    HIP_TRY(hipEventRecord(h->ev_join[p - 1], h->xstream[p - 1]));
+    HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join[p - 1], 0));
+  }
+  // the one tail of its own: the loss and the bucket sum as two launches, and K4 -- none of them guarded by the planned
+  // solve's skip word, and no CB_T_K4 mark (the form runs without profile markers)
+  hipLaunchKernelGGL(lg_finish_loss, dim3(1), dim3(256), 0, h->stream, h->loss_part, B * c.tiles_k1, S, h->dsq, h->dirsum, c.inv_n,
+                     c.loss);
+  hipLaunchKernelGGL(k3_reduce<double>, dim3((unsigned)((LL + 255) / 256)), dim3(256), 0, h->stream, h->Gt, B, LL, h->Mt,
+                     h->sym_counts ? LD : 0);
+  enqueue_k4(h, c, nullptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  return CB_OK;
+}
+
+// h->A (padded, symmetric) and h->dsq are filled.  Output: dQ (S x S, dQ = D^1/2 dA D^-1/2) when
+// `dA_padded` is false, else dL/dA itself as a padded LD x LD matrix.
+// `plan`: a warm solve enqueued as a device-controlled plan (eigh_planned_host.hip.h) instead of the host-driven loop; the
+// caller reads the record of solve `h->eseq` afterwards and repeats the evaluation without a plan if the solve stalled.
+static int large_eval(cb_bank *h, bool normalize, double *lossd, double *out, bool dA_padded, double *Pd,
+                      bool reuse_eigh = false, const EighPlan *plan = nullptr, int plan_first_slot = 0) {
+  const int LD = h->LD, B = Pd ? h->B : h->Bl;   // the loss visits live buckets only
+  const bool planned_now = plan && h->have_prev;
+  LargeBankForm f = choose_large_form(h, B, Pd != nullptr, out != nullptr, planned_now);
+  // (the bank kernels return at once when the planned solve in front of them stalled: EC_STALL)
+  const unsigned long long *skipw = planned_now ? h->ectl + (f.tb ? EC_SKIP : EC_STALL) : nullptr;
+  int rc = CB_OK;
+  if (planned_now) {
+    TbTableArgs tbt;   // (the bank's spectral tables ride on the solve's last launch)
+    if (f.tb) tbt = TbTableArgs{h->tb.ns, h->tb.nd, h->tb.ng, h->tb_tf[h->tb_set], h->tb_tg[h->tb_set], h->F, h->E, h->H};
+    rc = enqueue_planned_solve(h, *plan, ++h->eseq, plan_first_slot, f.tb ? h->tb.rho_max : 0.0, tbt);
+  }
+  else if (!(reuse_eigh && h->have_prev)) rc = large_eigh(h, true);   // reuse: same matrix as the previous call (CB_REUSE_EIGH)
+  if (rc != CB_OK) return rc;
+  if (f.tb && !planned_now) {   // (the host-driven solve: sigma is known now)
+    double sg = 0.0;
+    HIP_TRY(hipMemcpyAsync(&sg, h->sigma, sizeof sg, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (!tb_in_range(h, B, 2.0 * sg)) {
+      rc = tb_rebuild(h, B, 2.0 * sg);
+      if (rc != CB_OK) return rc;
+      if (h->tb_failed) f.tb = false;
+    }
+  }
+  if (f.tb) {   // (the form that runs: the time basis has no per-bucket form)
+    f.fused = f.accum = false;
+    f.kg = 1;
+  }
+  h->bank_tb = f.tb;
+  h->bank_fused = f.fused;
+  h->bank_accum = f.accum;
+  h->bank_kg = f.kg;
+  SlowScope scope_bank("large_eval: tables, bank, K4 enqueue");
+  if (!planned_now) mark(h, EV_EIGH);   // (a planned solve's last launch carries the mark)
+  const int tm = (LD + LG_TM - 1) / LG_TM, tn = (LD + LG_TN - 1) / LG_TN;
+  const LargeCall c{B, Pd ? h->t : h->t_live, normalize ? 1.0 / (h->comm ? h->n_global[0] : h->n_host[0]) : 1.0, lossd, out, Pd,
+                    dA_padded, planned_now, skipw, (size_t)LD * LD, tm * tn, tn * (tn + 1) / 2};
+  if (f.tb) return h->dtype == CB_MIXED ? enqueue_tb_bank<float>(h, f, c) : enqueue_tb_bank<double>(h, f, c);
+  if (f.n_parts > 1) return enqueue_stream_split_bank(h, f, c);
+  return with_format(h, Pd != nullptr, [&](auto t1, auto tg) {
+    using T1 = decltype(t1);
+    using TG = decltype(tg);
+    return f.fused ? enqueue_fused_bank<T1, TG>(h, f, c) : enqueue_split_bank<T1, TG>(h, f, c);
+  });
 }
 
 static int large_loss_grad(cb_bank *h, const double *Qd, const double *pid, bool normalize,
