@@ -9,6 +9,7 @@ from .bank import CherryBank  # noqa: F401
 from .evaluation import compute_log_likelihoods  # noqa: F401,E402
 from .phylogeny_estimation import fast_cherries  # noqa: F401,E402
 from ._cherryml_public_api import cherryml_public_api  # noqa: F401,E402
+from .simulation import simulate_msas  # noqa: F401,E402
 from .estimation import (RateMatrix, RateMatrixLearner, jtt_ipw, quantized_transitions_mle,  # noqa: F401
                          train_quantization)
 
@@ -17,5 +18,5 @@ __all__ = [
     "quantized_transitions_mle", "quantized_transitions_mle_vectorized_over_sites", "jtt_ipw",
     "learn_site_specific_rate_matrices", "cherryml_public_api", "compute_log_likelihoods", "fast_cherries",
     "io", "caching", "counting", "count_transitions", "count_co_transitions",
-    "lg_end_to_end_with_cherryml_optimizer", "coevolution_end_to_end_with_cherryml_optimizer",
+    "lg_end_to_end_with_cherryml_optimizer", "coevolution_end_to_end_with_cherryml_optimizer", "simulate_msas",
 ]

@@ -179,3 +179,32 @@ def write_probability_distribution(p: np.ndarray, states: List[str], path: str) 
     df = pd.DataFrame(np.asarray(p).reshape(-1), index=states, columns=["prob"])
     df.index.name = "state"
     df.to_csv(path, sep="\t", index=True)
+
+
+def _ensure_parent(path: str) -> None:
+    d = os.path.dirname(path)
+    if d != "" and not os.path.exists(d):
+        os.makedirs(d)
+
+
+def write_msa(msa, msa_path: str) -> None:
+    """">name\\nsequence\\n" per sequence, names sorted (reference: cherryml/io/_msa.py:78-89)."""
+    _ensure_parent(msa_path)
+    with open(msa_path, "w") as f:
+        f.write("".join(f">{name}\n{msa[name]}\n" for name in sorted(msa)))
+
+
+def write_site_rates(site_rates, site_rates_path: str) -> None:
+    """"<n> sites\\n" + the rates, space separated, no final newline (reference: cherryml/io/_site_rates.py:29-36)."""
+    _ensure_parent(site_rates_path)
+    with open(site_rates_path, "w") as f:
+        f.write(f"{len(site_rates)} sites\n" + " ".join(map(str, site_rates)))
+
+
+def write_contact_map(contact_map: np.ndarray, contact_map_path: str) -> None:
+    """"<n> sites\\n" + one row of 0 / 1 digits per site (reference: cherryml/io/_contact_map.py:34-44)."""
+    _ensure_parent(contact_map_path)
+    cm = np.asarray(contact_map)
+    with open(contact_map_path, "w") as f:
+        f.write(f"{cm.shape[0]} sites\n")
+        np.savetxt(f, cm, delimiter="", fmt="%i")

@@ -494,6 +494,40 @@ int cb_tl_model_destroy(cb_tl_model model);
 int cb_parse_count_matrices(const char *text, size_t len, int B, int S, double *q, double *C,
                             long long *label_off, int *label_len, int n_threads);
 
+/* ---- MSA simulation (cherryml/simulation/_simulate_msas.py:94-423, the reference's simulate.cpp) ---------------------
+ * The exact jump chain ("all_transitions") down every edge of every family, one GPU thread per (family, unit).  A unit is an
+ * independent site (Q1 / pi1, S1 states) or a contacting pair (Q2 / pi2, S1 * S1 states, pair state a * S1 + b); it evolves
+ * for elapsed = length * unit_rate on each edge (the reference runs pairs at rate 1: the caller passes 1 for them).
+ *
+ * Random stream (fixed, so that any restatement reproduces the output; independent of launch geometry and batching):
+ *   Philox4x32-10 (Random123 constants), key = (low, high) 32-bit words of the family seed, counter (u, v, j, 0) for draw j of
+ *   unit u at node v, v = the node's preorder index.  One block (x0, x1, x2, x3) gives two uniforms in (0, 1]:
+ *   a = ((x1 << 32 | x0) >> 11) * 2^-53 + 2^-54 and b likewise from (x3, x2).
+ *   Alias draw with a uniform u on a table of n columns: x = u * n, k = min(floor(x), n - 1), state k if x - k < prob[k],
+ *   else alias[k].
+ *   Root (v = 0): the alias draw on pi with a of counter (u, 0, 0, 0).
+ *   Edge into node v, from the parent's state s, t = 0, for j = 0, 1, ...: w = -log(a) / q_s with q_s = -Q[s][s]; stop unless
+ *   t + w < elapsed; else t += w and s = the alias draw on row s (weights: the off-diagonal rates of Q[s]) with b.
+ *   A row with no exit rate is absorbing.
+ * The alias tables are Vose's, built in double by cb_sim_alias_table (host only; zero weights are never drawn).
+ *
+ * cb_sim_model_create checks Q1 / pi1 (and Q2 / pi2, which may both be NULL: no pair units then), builds the tables and keeps
+ * them on `device` (2 <= S1 <= 64); with no GPU it fails -- there is no CPU path.  cb_sim_model_run simulates n_fam families
+ * in one launch: family f has n_nodes[f] nodes in preorder (parent[0] = -1, parent[v] < v; length[v] = length of the edge
+ * into v), n_sites[f] sites and n_units[f] units (unit_site_a / unit_site_b / unit_rate; unit_site_b = -1: an independent
+ * site) that cover every site exactly once; the per-node and per-unit arrays are the families' arrays concatenated in order.
+ * out receives, family after family, the states [n_nodes[f]][n_sites[f]] as int8 codes (a pair writes a and b into its two
+ * columns).  Everything is validated on the host before any upload (CB_EINVAL), including a bound on the expected number of
+ * jumps of a unit on one edge (1e7).  kernel_ms (may be NULL): the launch's device time.  One call at a time per model. */
+int cb_sim_alias_table(int n, const double *w, double *prob, int *alias);
+typedef struct cb_sim_model_s *cb_sim_model;
+int cb_sim_model_create(int device, int S1, const double *Q1, const double *pi1, const double *Q2, const double *pi2,
+                        cb_sim_model *out);
+int cb_sim_model_run(cb_sim_model model, int n_fam, const uint64_t *fam_seed, const int *n_nodes, const int *parent,
+                     const double *length, const int *n_sites, const int *n_units, const int *unit_site_a,
+                     const int *unit_site_b, const double *unit_rate, int8_t *out, double *kernel_ms);
+int cb_sim_model_destroy(cb_sim_model model);
+
 /* ---- FastCherries' cherry pairing, host only -------------------------------------------------------------
  * divide_and_pair of phylogeny_estimation/FastCherries/pairing_algorithms.cpp:77-175 on int8 sequences
  * [n][L] (state index, -1 unknown): the seeded divide-and-conquer over Hamming distances, with the
