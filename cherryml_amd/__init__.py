@@ -10,8 +10,9 @@ from .evaluation import compute_log_likelihoods  # noqa: F401,E402
 from .phylogeny_estimation import fast_cherries  # noqa: F401,E402
 from ._cherryml_public_api import cherryml_public_api  # noqa: F401,E402
 from .simulation import simulate_msas  # noqa: F401,E402
-from .estimation import (RateMatrix, RateMatrixLearner, jtt_ipw, quantized_transitions_mle,  # noqa: F401
+from .estimation import (EStep, RateMatrix, RateMatrixLearner, em_lg, jtt_ipw, quantized_transitions_mle,  # noqa: F401
                          train_quantization)
+from .estimation_end_to_end import lg_end_to_end_with_em_optimizer  # noqa: F401,E402
 
 __all__ = [
     "CherryBank", "RateMatrix", "RateMatrixLearner", "train_quantization",
@@ -19,4 +20,5 @@ __all__ = [
     "learn_site_specific_rate_matrices", "cherryml_public_api", "compute_log_likelihoods", "fast_cherries",
     "io", "caching", "counting", "count_transitions", "count_co_transitions",
     "lg_end_to_end_with_cherryml_optimizer", "coevolution_end_to_end_with_cherryml_optimizer", "simulate_msas",
+    "EStep", "em_lg", "lg_end_to_end_with_em_optimizer",
 ]

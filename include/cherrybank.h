@@ -528,6 +528,31 @@ int cb_sim_model_run(cb_sim_model model, int n_fam, const uint64_t *fam_seed, co
                      const int *unit_site_b, const double *unit_rate, int8_t *out, double *kernel_ms);
 int cb_sim_model_destroy(cb_sim_model model);
 
+/* ---- full-tree EM, the E-step on a resident handle (S <= 32; the 20-state model) ---------------------------------------------
+ * Stands in for the E-step the reference delegates to Historian / XRATE (cherryml/estimation/_em_lg.py:251-330,
+ * estimation_end_to_end/_em.py:33-120): the states at the internal nodes are the missing data, independent sites evolve under Q
+ * at their site rate, and every edge length x site rate is put on the quantisation grid (the reference's nearest-point rule,
+ * cherryml/utils.py:35-56, clamped to the grid's ends), so that the edge above node v carries P_beta = expm(grid[beta] Q).
+ *
+ * cb_em_create validates everything on the host before any device work -- 2 <= S <= 32, a positive strictly increasing grid of B
+ * points, parent arrays that form a tree (one root with parent -1, every node reachable), finite lengths >= 0, site rates >= 0,
+ * leaf state codes in [-1, S) -- then uploads, once, the n_fam families: family f has n_nodes[f] nodes (parent[v], length[v] = the edge
+ * into v, any node order), n_units[f] sites (unit_rate) and codes [n_nodes[f]][n_units[f]] (int8 state, -1 = gap: all states;
+ * only LEAF rows are read, internal rows such as simulate_msas writes them are ignored); the per-node / per-unit / per-code
+ * arrays are the families' arrays concatenated in order.  With no GPU it fails (CB_EHIP): there is no CPU path.
+ *
+ * cb_em_estep sends only Q [S][S] (any rate matrix) and the root distribution pi_root [S] and returns
+ *   counts [B][S][S]  E_beta[a][b] = sum over the edges (p -> v) and sites in bucket beta of P(x_p = a, x_v = b | leaves),
+ *   ll     [sum n_units] (may be NULL) the log-likelihood of every site, fam_ll [n_fam] (may be NULL) their sums per family,
+ *   kernel_ms (may be NULL) the device time of the step (bank, passes, accumulation).
+ * The accumulation runs over fixed per-bucket task lists without atomics: two calls with the same input give bitwise-equal
+ * counts.  One call at a time per handle. */
+typedef struct cb_em_s *cb_em;
+int cb_em_create(int device, int S, int B, const double *grid, int n_fam, const int *n_nodes, const int *parent,
+                 const double *length, const int *n_units, const double *unit_rate, const int8_t *codes, cb_em *out);
+int cb_em_estep(cb_em h, const double *Q, const double *pi_root, double *counts, double *ll, double *fam_ll, double *kernel_ms);
+int cb_em_destroy(cb_em h);
+
 /* ---- FastCherries' cherry pairing, host only -------------------------------------------------------------
  * divide_and_pair of phylogeny_estimation/FastCherries/pairing_algorithms.cpp:77-175 on int8 sequences
  * [n][L] (state index, -1 unknown): the seeded divide-and-conquer over Hamming distances, with the
