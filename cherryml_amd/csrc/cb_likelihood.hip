@@ -2,130 +2,207 @@
 #include "cb_internal.hip.h"
 #include "common.hip.h"
 #include "likelihood.hip.h"
+#include "tl_layout.h"
 
-// ---------------------------------------------------------------- held-out likelihood
-namespace {
-// host-side view of one family: validated tree, levels (nodes of equal height), children in post-order
-struct TlFamily {
-  int n_nodes = 0, n_units = 0, n_cats = 0, root = 0, n_levels = 0;
-  std::vector<int> level_ptr, level_nodes, child_ptr, child_idx, nchild;
-  std::vector<int> slot;   // bank slot of a node when the bank holds the INTERNAL non-root nodes only (-1: none); n_int of them
-  int n_int = 0;
+// ---- the model resident on the device ------------------------------------------------------------------------------------
+// cb_tree_likelihood[_batch] takes the model with every call, like the reference's per-family processes
+// (evaluation/_likelihood.py:474-600): Q uploaded, a counts-free expm handle created, 2.6 GB of transition bank and the message
+// buffer allocated and freed, the model's eigendecomposition recomputed -- 21 ms per 1024-leaf family of the 400-state pair model
+// around 10.7 ms of kernels.  A cb_tl_model keeps all of that between calls.
+struct cb_tl_model_s {
+  int device = 0, S = 0, S1 = 0;
+  bool reversible = false;                  // made with pi_rev: the bank comes from the symmetric eigendecomposition
+  double *dQ = nullptr, *dpi = nullptr, *dproot = nullptr;
+  double *dP = nullptr, *dmsg = nullptr;    // transition bank [slot][S][S] and messages, grown on demand
+  size_t cap_P = 0, cap_msg = 0, cap_bank = 0;
+  cb_handle hl = nullptr;                   // the counts-free expm handle, cap_bank slots
+  bool eigh_done = false;
+  // S > 64, reversible: the leaves' tables (tl_tables_kernel), built behind the model's first eigensolve
+  double *dTU = nullptr, *dTA = nullptr;
+  bool tables_done = false;
 };
 
-int tl_prepare(int S, int S1, int n_nodes, const int *postorder, const int *parent, const double *length, int n_cats,
-               const double *cat_rate, int n_units, const int *unit_cat, const int8_t *code_a, const int8_t *code_b,
-               TlFamily &f) {
-  if (n_nodes < 1 || n_cats < 1 || n_units < 1)
-    return fail(CB_EINVAL, "cb_tree_likelihood: bad sizes (nodes = %d, categories = %d, units = %d)", n_nodes, n_cats, n_units);
-  if (S > 64 && n_cats != 1)
-    return fail(CB_EUNSUPPORTED, "cb_tree_likelihood: S > 64 takes one rate category (the reference evaluates pairs "
-                "of sites at rate 1, _likelihood.py:214-230)");
-  f.n_nodes = n_nodes; f.n_units = n_units; f.n_cats = n_cats;
-  // ---- tree: heights, levels, children in post-order (= the reference's child order, _tree.py traversal)
-  const int root = postorder[n_nodes - 1];
-  std::vector<int> height(n_nodes, 0), seen(n_nodes, 0);
-  f.nchild.assign(n_nodes, 0);
-  for (int i = 0; i < n_nodes; ++i) {
-    const int v = postorder[i];
-    if (v < 0 || v >= n_nodes || seen[v]) return fail(CB_EINVAL, "cb_tree_likelihood: postorder is not a permutation");
-    seen[v] = 1;
-    const int p = parent[v];
-    if (i == n_nodes - 1) {
-      if (p != -1) return fail(CB_EINVAL, "cb_tree_likelihood: the last node of postorder must be the root (parent -1)");
-      break;
+namespace {
+// the device side of one call's arrays (TlLayout's offsets apply), or of one family of it (tl_family_view)
+struct TlDev {
+  double *dll = nullptr;
+  const int *duc = nullptr;
+  const int8_t *dca = nullptr, *dcb = nullptr;
+  const int *dlev = nullptr, *dcp = nullptr, *dci = nullptr;
+  const double *dt_all = nullptr, *dt_node = nullptr;
+  const int *dslot = nullptr;
+};
+
+TlDev tl_family_view(const TlDev &d, const TlLayout &L, int f) {
+  const size_t on = L.off_n[f], ou = L.off_u[f], oc = L.off_c[f];
+  TlDev v;
+  v.dll = d.dll + ou; v.duc = d.duc + ou; v.dca = d.dca + oc; v.dcb = d.dcb ? d.dcb + oc : nullptr;
+  v.dlev = d.dlev + on; v.dcp = d.dcp + on + f; v.dci = d.dci + on;
+  v.dt_all = d.dt_all + L.off_t[f];
+  if (L.factored) { v.dt_node = d.dt_node + on; v.dslot = d.dslot + on; }
+  return v;
+}
+
+// The timing events of one call: the whole timed region (ev0 .. ev1) and a marker pair around each family's pruning.
+// Whatever was created is destroyed on every way out of the call.
+struct TlTimer {
+  const bool on;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  std::vector<hipEvent_t> marks;   // (begin, end) per timed family
+  explicit TlTimer(bool on_) : on(on_) {}
+  TlTimer(const TlTimer &) = delete;
+  ~TlTimer() {
+    for (hipEvent_t ev : marks) (void)hipEventDestroy(ev);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+  }
+  int start() {
+    if (!on) return CB_OK;
+    HIP_TRY(hipEventCreate(&ev0));
+    HIP_TRY(hipEventCreate(&ev1));
+    HIP_TRY(hipStreamSynchronize(0));   // the timed region starts with resident inputs
+    HIP_TRY(hipEventRecord(ev0, 0));
+    return CB_OK;
+  }
+  // both markers of a family or neither
+  bool family_begin() {
+    hipEvent_t b = nullptr, e = nullptr;
+    if (!on || hipEventCreate(&b) != hipSuccess) return false;
+    if (hipEventCreate(&e) != hipSuccess) {
+      (void)hipEventDestroy(b);
+      return false;
     }
-    if (p < 0 || p >= n_nodes || seen[p]) return fail(CB_EINVAL, "cb_tree_likelihood: node %d precedes its child %d", p, v);
-    if (!(length[v] >= 0.0) || !std::isfinite(length[v])) return fail(CB_EINVAL, "cb_tree_likelihood: length[%d] = %g", v, length[v]);
-    height[p] = std::max(height[p], height[v] + 1);
-    f.nchild[p]++;
+    marks.push_back(b);
+    marks.push_back(e);
+    (void)hipEventRecord(b, 0);
+    return true;
   }
-  f.root = root;
-  f.child_ptr.assign(n_nodes + 1, 0);
-  f.child_idx.assign(std::max(n_nodes - 1, 1), 0);
-  std::vector<int> fill(n_nodes, 0);
-  for (int v = 0; v < n_nodes; ++v) f.child_ptr[v + 1] = f.child_ptr[v] + f.nchild[v];
-  for (int i = 0; i + 1 < n_nodes; ++i) {
-    const int v = postorder[i], p = parent[v];
-    f.child_idx[f.child_ptr[p] + fill[p]++] = v;
+  void family_end() { (void)hipEventRecord(marks.back(), 0); }
+  // waits for the stream; kernel_ms[0] = the region, kernel_ms[1] = the sum over the families' marker pairs
+  int finish(double *kernel_ms, int rc) {
+    if (!on) return rc;
+    float ms = 0.f;
+    hipError_t e = hipEventRecord(ev1, 0);
+    if (e == hipSuccess) e = hipEventSynchronize(ev1);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
+    double ms_prune = 0.0;
+    for (size_t i = 0; i + 1 < marks.size(); i += 2) {
+      float mp = 0.f;
+      if (hipEventElapsedTime(&mp, marks[i], marks[i + 1]) == hipSuccess) ms_prune += mp;
+    }
+    kernel_ms[0] = ms;
+    kernel_ms[1] = ms_prune;
+    if (e != hipSuccess && rc == CB_OK) rc = fail(CB_EHIP, "cb_tree_likelihood: %s", hipGetErrorString(e));
+    return rc;
   }
-  f.n_levels = height[root] + 1;
-  f.level_ptr.assign(f.n_levels + 1, 0);
-  f.level_nodes.assign(n_nodes, 0);
-  for (int v = 0; v < n_nodes; ++v) f.level_ptr[height[v] + 1]++;
-  for (int l = 0; l < f.n_levels; ++l) f.level_ptr[l + 1] += f.level_ptr[l];
-  {
-    std::vector<int> at(f.level_ptr.begin(), f.level_ptr.end() - 1);
-    for (int i = 0; i < n_nodes; ++i) f.level_nodes[at[height[postorder[i]]]++] = postorder[i];
+};
+
+int tl_grow(double *&p, size_t &cap, size_t need, const char *what) {
+  if (need <= cap) return CB_OK;
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  cap = 0;
+  if (hipMalloc((void **)&p, need * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(CB_ENOMEM, "cb_tree_likelihood: %zu bytes for the %s", need * sizeof(double), what);
   }
-  f.slot.assign(n_nodes, -1);
-  f.n_int = 0;
-  for (int v = 0; v < n_nodes; ++v)
-    if (f.nchild[v] > 0 && v != root) f.slot[v] = f.n_int++;
-  for (int u = 0; u < n_units; ++u)
-    if (unit_cat[u] < 0 || unit_cat[u] >= n_cats) return fail(CB_EINVAL, "cb_tree_likelihood: unit_cat[%d] = %d", u, unit_cat[u]);
-  for (int c = 0; c < n_cats; ++c)
-    if (!(cat_rate[c] >= 0.0) || !std::isfinite(cat_rate[c])) return fail(CB_EINVAL, "cb_tree_likelihood: cat_rate[%d] = %g", c, cat_rate[c]);
-  const int alpha = S1 > 0 ? S1 : S;
-  for (int v = 0; v < n_nodes; ++v)
-    if (!f.nchild[v])
-      for (int u = 0; u < n_units; ++u) {
-        const size_t i = (size_t)v * n_units + u;
-        if (code_a[i] >= alpha || (S1 > 0 && code_b[i] >= alpha)) return fail(CB_EINVAL, "cb_tree_likelihood: state code out of range at node %d unit %d", v, u);
-      }
+  cap = need;
   return CB_OK;
 }
 
-// the pruning of one family: one launch per height over (nodes of that height) x (blocks of units), stream 0
-struct TlFactored {   // leaves from the eigendecomposition (tl_leaf_mfma_kernel); slot == nullptr: the round-5 path
-  const int *slot = nullptr;
-  const double *tnode = nullptr, *U = nullptr, *lam = nullptr, *dsq = nullptr, *sigma = nullptr, *TU = nullptr, *TA = nullptr;
-  int LD = 0;
-};
-int tl_prune(int S, int S1, const TlFamily &f, const double *dP, int cat_stride_nodes, const double *dproot, const int *duc,
-             const int8_t *dca, const int8_t *dcb, const int *dlev, const int *dcp, const int *dci, double *dmsg, double *dll,
-             int NU, const TlFactored &fx = TlFactored{}) {
-  TlArgs a{};
-  a.slot = fx.slot; a.tnode = fx.tnode; a.U = fx.U; a.lam = fx.lam; a.dsq = fx.dsq; a.sigma = fx.sigma; a.TU = fx.TU; a.TA = fx.TA; a.LD = fx.LD;
-  a.S = S; a.S1 = S1; a.n_nodes = cat_stride_nodes; a.n_units = f.n_units; a.NU = NU; a.root = f.root;
-  a.child_ptr = dcp; a.child_idx = dci; a.P = dP; a.unit_cat = duc;
-  a.code_a = reinterpret_cast<const signed char *>(dca);
-  a.code_b = reinterpret_cast<const signed char *>(dcb);
-  a.pi_root = dproot; a.msg = dmsg; a.ll = dll;
-  const int nt = (S + 15) / 16, Sp = nt * 16;
-  const int NB = f.n_units > 16 ? 2 : 1;   // unit blocks of 16 per workgroup
+// What all families AND all calls on a model share, sized for the largest family met so far: the transition bank's and the
+// messages' buffers (2.6 GB for a 1024-leaf family of the 400-state pair model) ...
+int tl_model_reserve(cb_tl_model_s &m, const TlLayout &L) {
+  const int rc = tl_grow(m.dP, m.cap_P, L.max_bank * m.S * m.S, "transition bank");
+  return rc != CB_OK ? rc : tl_grow(m.dmsg, m.cap_msg, L.max_msg, "messages");
+}
+
+// ... and one counts-free handle: a single "site" whose buckets are a family's bank slots.  A new handle has no decomposition
+// yet, so the eigensolve and the leaves' tables that hang on it are due again.
+int tl_model_handle(cb_tl_model_s &m, const TlLayout &L) {
+  if (m.hl && L.max_bank <= m.cap_bank) return CB_OK;
+  if (m.hl) cb_destroy(m.hl);
+  m.hl = nullptr;
+  m.eigh_done = false;
+  m.tables_done = false;   // (the same solver on the same matrix would give the same tables: not a promise kept here)
+  const std::vector<double> t0(L.max_bank, 0.0);
+  int rc = cb_create(m.device, m.S, 1, (int)L.max_bank, CB_F64, t0.data(), nullptr, CB_EXPM_ONLY, &m.hl);
+  if (rc == CB_OK) rc = cb_set_stream(m.hl, nullptr, 0);
+  if (rc == CB_OK) m.cap_bank = L.max_bank;
+  return rc;
+}
+
+// the caller's codes and categories and the trees, before the timed region starts
+int tl_upload_inputs(CbDevBufs &bufs, const TlCall &c, const TlLayout &L, bool pairs, TlDev &d) {
+  int rc = CB_OK;
+  const size_t n_units = L.off_u[c.n_fam], n_codes = L.off_c[c.n_fam];
+  d.dll = bufs.up<double>(nullptr, n_units, rc);
+  d.duc = bufs.up(c.unit_cat, n_units, rc);
+  d.dca = bufs.up(c.code_a, n_codes, rc);
+  d.dcb = pairs ? bufs.up(c.code_b, n_codes, rc) : nullptr;
+  d.dlev = bufs.up(L.level_nodes.data(), L.level_nodes.size(), rc);
+  d.dcp = bufs.up(L.child_ptr.data(), L.child_ptr.size(), rc);
+  d.dci = bufs.up(L.child_idx.data(), L.child_idx.size(), rc);
+  return rc;
+}
+
+// rate x length of ALL families, inside the timed region: a family's bank then starts behind the previous family's pruning on
+// the stream without the host waiting for it
+int tl_upload_times(CbDevBufs &bufs, const TlLayout &L, TlDev &d) {
+  int rc = CB_OK;
+  d.dt_all = bufs.up(L.t_all.data(), L.t_all.size(), rc);
+  d.dt_node = L.factored ? bufs.up(L.t_node.data(), L.t_node.size(), rc) : nullptr;
+  d.dslot = L.factored ? bufs.up(L.slot_all.data(), L.slot_all.size(), rc) : nullptr;
+  return rc;
+}
+
+// family f's transition bank expm(t Q), one [S][S] matrix per bank slot, by the bank's own expm kernels (d: the family's view); the reversible
+// bank of S > 32 keeps the model's eigendecomposition from the first family on
+int tl_family_bank(cb_tl_model_s &m, const TlLayout &L, int f, const TlDev &d) {
+  int rc = cb_internal_set_times(m.hl, L.t_all.data() + L.off_t[f], (int)L.fam[f].n_bank, d.dt_all);
+  if (rc != CB_OK) return rc;
+  const int reuse = m.S > 32 && m.eigh_done && m.dpi ? CB_REUSE_EIGH : 0;
+  rc = cb_internal_expm_bank(m.hl, m.dQ, m.dpi, CB_PTR_DEVICE | CB_NO_SYNC | reuse, m.dP);
+  if (rc == CB_OK) m.eigh_done = true;
+  return rc;
+}
+
+// the leaves' tables of a factored model: once per decomposition, behind its eigensolve on the stream
+int tl_leaf_tables(cb_tl_model_s &m, const CbSpectral &sp) {
+  if (m.tables_done) return CB_OK;
+  const int nJ = m.S + (m.S1 > 0 ? 2 * m.S1 : 0) + 1;
+  if (!m.dTU && (hipMalloc((void **)&m.dTU, (size_t)nJ * sp.LD * sizeof(double)) != hipSuccess ||
+                 hipMalloc((void **)&m.dTA, (size_t)nJ * sp.LD * sizeof(double)) != hipSuccess)) {
+    (void)hipGetLastError();
+    return fail(CB_ENOMEM, "cb_tree_likelihood: device allocation failed");
+  }
+  hipLaunchKernelGGL(tl_tables_kernel, dim3(nJ), dim3(256), 0, 0, m.S, m.S1, sp.LD, nJ, sp.U, sp.A, sp.dsq, m.dTU, m.dTA);
+  m.tables_done = true;
+  return CB_OK;
+}
+
+// the levels of one family with NB blocks of 16 units per workgroup: one launch per height over (nodes of that height) x
+// (blocks of units), stream 0.  a.slot != nullptr: the leaves come from the eigendecomposition (tl_leaf_mfma_kernel).
+template <int NB>
+int tl_prune_levels(const TlFamily &F, TlArgs a, const int *dlev) {
+  const int S = a.S, Sp = (S + 15) / 16 * 16;
   const size_t lds = ((size_t)(Sp * NB + Sp / 4 + NB) * 16 + (size_t)TL_NW * NB * 16) * sizeof(double);
-  const size_t lds_leaf = ((size_t)TL_LR * (S + 1) + TL_LR + (size_t)TL_LR * 2 * S1) * sizeof(double) + 2 * (size_t)f.n_units;
+  const size_t lds_leaf = ((size_t)TL_LR * (S + 1) + TL_LR + (size_t)TL_LR * 2 * a.S1) * sizeof(double) + 2 * (size_t)F.n_units;
   if (S > 64 && lds_leaf > 160 * 1024)
-    return fail(CB_EUNSUPPORTED, "cb_tree_likelihood: %d units per family at S > 64 (at most 50 000)", f.n_units);
-  const void *mfma_fn = NB == 2 ? reinterpret_cast<const void *>(tl_mfma_kernel<2>)
-                                : reinterpret_cast<const void *>(tl_mfma_kernel<1>);
-  const void *leaf_fn = NB == 2 ? reinterpret_cast<const void *>(tl_leaf_mfma_kernel<2>)
-                                : reinterpret_cast<const void *>(tl_leaf_mfma_kernel<1>);
-  if (S > 64 && (hipFuncSetAttribute(mfma_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-                 hipFuncSetAttribute(leaf_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-                 hipFuncSetAttribute(reinterpret_cast<const void *>(tl_leaf_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_leaf) != hipSuccess))
+    return fail(CB_EUNSUPPORTED, "cb_tree_likelihood: %d units per family at S > 64 (at most 50 000)", F.n_units);
+  const auto set_lds = [](auto *kernel, size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  };
+  if (S > 64 && (set_lds(tl_mfma_kernel<NB>, lds) != hipSuccess || set_lds(tl_leaf_mfma_kernel<NB>, lds) != hipSuccess ||
+                 set_lds(tl_leaf_kernel, lds_leaf) != hipSuccess))
     return fail(CB_EHIP, "cb_tree_likelihood: cannot reserve %zu bytes of LDS", lds);
-  for (int l = 0; l < f.n_levels; ++l) {
-    const int nl = f.level_ptr[l + 1] - f.level_ptr[l];
-    // height 0 = the leaves (never the root when the tree has an edge): gathered, not multiplied
-    const bool leaves = S > 64 && l == 0 && f.n_levels > 1;
-    const bool leaves_fx = leaves && fx.slot != nullptr;
-    a.n_blocks = (leaves && !leaves_fx) ? 1 : S > 64 ? (f.n_units + 16 * NB - 1) / (16 * NB) : (f.n_units + 64 / S - 1) / (64 / S);
+  for (int l = 0; l < F.n_levels; ++l) {
+    const int nl = F.level_ptr[l + 1] - F.level_ptr[l];
+    // height 0 = the leaves (never the root when the tree has an edge): gathered or factored, not multiplied
+    const bool leaves = S > 64 && l == 0 && F.n_levels > 1;
+    const bool leaves_fx = leaves && a.slot != nullptr;
+    a.n_blocks = (leaves && !leaves_fx) ? 1 : S > 64 ? (F.n_units + 16 * NB - 1) / (16 * NB) : (F.n_units + 64 / S - 1) / (64 / S);
     a.RS = 1;
-    if (leaves_fx) {
-      const int per_launch = std::max(1, (1 << 30) / a.n_blocks);
-      for (int y0 = 0; y0 < nl; y0 += per_launch) {
-        TlArgs b = a;
-        b.level_nodes = dlev + f.level_ptr[l] + y0;
-        b.n_level = std::min(per_launch, nl - y0);
-        const dim3 grid((unsigned)b.n_level * (unsigned)a.n_blocks);
-        if (NB == 2) hipLaunchKernelGGL(tl_leaf_mfma_kernel<2>, grid, dim3(TL_NW * 64), lds, 0, b);
-        else hipLaunchKernelGGL(tl_leaf_mfma_kernel<1>, grid, dim3(TL_NW * 64), lds, 0, b);
-      }
-      continue;
-    }
     if (S > 64 && !leaves) {   // small levels: split the rows of a node over 2 or 4 workgroups (one per CU)
       const long wgs = (long)nl * a.n_blocks;
       a.RS = wgs * 4 <= 256 ? 4 : wgs * 2 <= 256 ? 2 : 1;
@@ -134,236 +211,70 @@ int tl_prune(int S, int S1, const TlFamily &f, const double *dP, int cat_stride_
     const int per_launch = std::max(1, (1 << 30) / per_node);   // keep the 1-D grid below 2^30 workgroups
     for (int y0 = 0; y0 < nl; y0 += per_launch) {
       TlArgs b = a;
-      b.level_nodes = dlev + f.level_ptr[l] + y0;
+      b.level_nodes = dlev + F.level_ptr[l] + y0;
       b.n_level = std::min(per_launch, nl - y0);
       const dim3 grid((unsigned)b.n_level * (unsigned)per_node);
-      if (leaves)
+      if (leaves_fx)
+        hipLaunchKernelGGL(tl_leaf_mfma_kernel<NB>, grid, dim3(TL_NW * 64), lds, 0, b);
+      else if (leaves)
         hipLaunchKernelGGL(tl_leaf_kernel, grid, dim3(TL_LT), lds_leaf, 0, b);
-      else if (S > 64 && NB == 2)
-        hipLaunchKernelGGL(tl_mfma_kernel<2>, grid, dim3(TL_NW * 64), lds, 0, b);
       else if (S > 64)
-        hipLaunchKernelGGL(tl_mfma_kernel<1>, grid, dim3(TL_NW * 64), lds, 0, b);
+        hipLaunchKernelGGL(tl_mfma_kernel<NB>, grid, dim3(TL_NW * 64), lds, 0, b);
       else
         hipLaunchKernelGGL(tl_group_kernel, grid, dim3(64), 0, 0, b);
     }
   }
   return CB_OK;
 }
-}  // namespace
 
-// ---- the model resident on the device (round 6; VERDICT r5 "missing 3") --------------------------------------------------------
-// cb_tree_likelihood[_batch] takes the model with every call, like the reference's per-family processes
-// (evaluation/_likelihood.py:474-600): Q uploaded, a counts-free expm handle created, 2.6 GB of transition bank and the message
-// buffer allocated and freed, the model's eigendecomposition recomputed -- 21 ms per 1024-leaf family of the 400-state pair model
-// around 10.7 ms of kernels.  A cb_tl_model keeps all of that between calls.
-struct cb_tl_model_s {
-  int device = 0, S = 0, S1 = 0, Lrep = 0;
-  std::vector<double> Q, pi_rev;            // host copies (S <= 32 replicates them per rate category on demand)
-  double *dQ = nullptr, *dpi = nullptr, *dproot = nullptr;
-  double *dP = nullptr, *dmsg = nullptr;    // transition bank [cat][node][S][S] and messages, grown on demand
-  size_t cap_P = 0, cap_msg = 0, cap_bank = 0;
-  cb_handle hl = nullptr;                   // S > 32: the counts-free expm handle
-  bool eigh_done = false;
-  // S > 64, reversible: the leaves' tables (tl_tables_kernel), built behind the model's first eigensolve
-  double *dTU = nullptr, *dTA = nullptr;
-  bool tables_done = false;
-};
+// the pruning of one family; d: the family's view of the call's device arrays; sp: the decomposition the factored leaves take
+// their operands from (empty otherwise: the leaves gather from the bank, tl_leaf_kernel)
+int tl_prune(const cb_tl_model_s &m, const TlFamily &F, const TlDev &d, const CbSpectral &sp) {
+  TlArgs a{};
+  a.slot = d.dslot; a.tnode = d.dt_node;
+  a.U = sp.U; a.lam = sp.lam; a.dsq = sp.dsq; a.sigma = sp.sigma; a.TU = m.dTU; a.TA = m.dTA; a.LD = sp.LD;
+  a.S = m.S; a.S1 = m.S1; a.n_nodes = F.n_nodes; a.n_units = F.n_units; a.NU = F.NU; a.root = F.root;
+  a.child_ptr = d.dcp; a.child_idx = d.dci; a.P = m.dP; a.unit_cat = d.duc;
+  a.code_a = reinterpret_cast<const signed char *>(d.dca);
+  a.code_b = reinterpret_cast<const signed char *>(d.dcb);
+  a.pi_root = m.dproot; a.msg = m.dmsg; a.ll = d.dll;
+  return F.n_units > 16 ? tl_prune_levels<2>(F, a, d.dlev) : tl_prune_levels<1>(F, a, d.dlev);
+}
 
-// One run of the pruning over MANY families on a resident model.  MANY families under ONE model in one call (the reference maps families over a process pool,
-// evaluation/_likelihood.py:474-600 / utils.py:59-67).  Family f: n_nodes[f] nodes, n_units[f] units, n_cats[f]
-// rate categories; postorder / parent / length (node indices local to the family), cat_rate, unit_cat, code_a /
-// code_b ([n_nodes[f]][n_units[f]]) and ll are the families' arrays concatenated in order.  What the batch shares:
-// the model's eigendecomposition -- for S > 32 (the 400-state pair model: 3 ms cold per family) ONE counts-free
-// bank handle serves all families (new branch lengths per family, eigensolve once) -- the uploads of Q / pi, and
-// the message buffer.  S > 32 with a reversible Q: all branch lengths are uploaded once and a family's bank is
-// enqueued behind the previous family's pruning without a host wait; the general (non-reversible) bank reads one
-// norm back per family, and for S <= 32 a handle is made (and waited for) per family.  Results equal
-// cb_tree_likelihood's.
-static int tl_run(cb_tl_model_s &m, int n_fam, const int *n_nodes, const int *postorder, const int *parent, const double *length,
-                  const int *n_cats, const double *cat_rate, const int *n_units, const int *unit_cat, const int8_t *code_a,
-                  const int8_t *code_b, double *ll, double *kernel_ms) {
-  if (!n_nodes || !postorder || !parent || !length || !n_cats || !cat_rate || !n_units || !unit_cat || !code_a || !ll)
-    return fail(CB_EINVAL, "cb_tree_likelihood: NULL argument");
-  const int device = m.device, S = m.S, S1 = m.S1;
-  if (n_fam < 1) return fail(CB_EINVAL, "cb_tree_likelihood: bad sizes (S = %d, families = %d)", S, n_fam);
-  if (S1 > 0 && !code_b) return fail(CB_EINVAL, "cb_tree_likelihood: pair model needs S = S1 * S1 and code_b");
-  const bool factored = S > 64 && !m.pi_rev.empty();
-  std::vector<TlFamily> fam(n_fam);
-  std::vector<size_t> off_n(n_fam + 1, 0), off_u(n_fam + 1, 0), off_c(n_fam + 1, 0), off_k(n_fam + 1, 0);
-  int rc = CB_OK, max_nodes = 0;
-  size_t max_msg = 0, max_bank = 0;
-  for (int f = 0; f < n_fam; ++f) {
-    if (n_nodes[f] < 1 || n_units[f] < 1 || n_cats[f] < 1) return fail(CB_EINVAL, "cb_tree_likelihood: family %d has bad sizes", f);
-    rc = tl_prepare(S, S1, n_nodes[f], postorder + off_n[f], parent + off_n[f], length + off_n[f], n_cats[f],
-                    cat_rate + off_k[f], n_units[f], unit_cat + off_u[f], code_a + off_c[f],
-                    code_b ? code_b + off_c[f] : nullptr, fam[f]);
-    if (rc != CB_OK) return rc;
-    off_n[f + 1] = off_n[f] + n_nodes[f];
-    off_u[f + 1] = off_u[f] + n_units[f];
-    off_c[f + 1] = off_c[f] + (size_t)n_nodes[f] * n_units[f];
-    off_k[f + 1] = off_k[f] + n_cats[f];
-    const int NU = S > 64 ? (n_units[f] + 31) / 32 * 32 : n_units[f];   // (tl_mfma_kernel: 16 or 32 unit columns per workgroup)
-    max_nodes = std::max(max_nodes, n_nodes[f]);
-    max_msg = std::max(max_msg, (size_t)n_nodes[f] * S * NU);
-    // (S > 64 with a reversible model: the bank holds the INTERNAL non-root nodes only -- the leaves take their messages from the
-    // eigendecomposition -- at least one slot, so that a family of leaves still triggers the model's eigensolve)
-    max_bank = std::max(max_bank, factored ? (size_t)std::max(fam[f].n_int, 1) : (size_t)n_cats[f] * n_nodes[f]);
-  }
-  const bool large = S > 32;
-  const size_t SS = (size_t)S * S;
-  HIP_TRY(hipSetDevice(device));
-  CbDevBufs d;
-  // shared by all families AND all calls on this model: Q / pi on the device, the transition bank's and the messages' buffers
-  // (2.6 GB for a 1024-leaf family of the 400-state pair model: allocating and freeing that per call was 8 of its 21 ms)
-  if (max_bank * SS > m.cap_P) {
-    if (m.dP) (void)hipFree(m.dP);
-    m.dP = nullptr;
-    m.cap_P = 0;
-    if (hipMalloc((void **)&m.dP, max_bank * SS * sizeof(double)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(CB_ENOMEM, "cb_tree_likelihood: %zu bytes for the transition bank", max_bank * SS * sizeof(double));
-    }
-    m.cap_P = max_bank * SS;
-  }
-  if (max_msg > m.cap_msg) {
-    if (m.dmsg) (void)hipFree(m.dmsg);
-    m.dmsg = nullptr;
-    m.cap_msg = 0;
-    if (hipMalloc((void **)&m.dmsg, max_msg * sizeof(double)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(CB_ENOMEM, "cb_tree_likelihood: %zu bytes for the messages", max_msg * sizeof(double));
-    }
-    m.cap_msg = max_msg;
-  }
-  const double *dQ = m.dQ, *dpi = m.dpi, *dproot = m.dproot;
-  double *dP = m.dP, *dmsg = m.dmsg;
-  double *dll = d.up<double>(nullptr, off_u[n_fam], rc);
-  const int *duc = d.up(unit_cat, off_u[n_fam], rc);
-  const int8_t *dca = d.up(code_a, off_c[n_fam], rc);
-  const int8_t *dcb = S1 > 0 ? d.up(code_b, off_c[n_fam], rc) : nullptr;
-  // per-family tree arrays, concatenated
-  std::vector<int> lev_all(off_n[n_fam]), cp_all(off_n[n_fam] + n_fam), ci_all(off_n[n_fam]);
-  for (int f = 0; f < n_fam; ++f) {
-    std::copy(fam[f].level_nodes.begin(), fam[f].level_nodes.end(), lev_all.begin() + off_n[f]);
-    std::copy(fam[f].child_ptr.begin(), fam[f].child_ptr.end(), cp_all.begin() + off_n[f] + f);
-    std::copy(fam[f].child_idx.begin(), fam[f].child_idx.begin() + std::max(n_nodes[f] - 1, 0), ci_all.begin() + off_n[f]);
-  }
-  const int *dlev = d.up(lev_all.data(), lev_all.size(), rc), *dcp = d.up(cp_all.data(), cp_all.size(), rc);
-  const int *dci = d.up(ci_all.data(), ci_all.size(), rc);
+// One run of the pruning over the families of a call that tl_check_call has passed, on a resident model (the reference maps
+// families over a process pool, evaluation/_likelihood.py:474-600 / utils.py:59-67).  The families share the model's
+// buffers and its one counts-free bank handle: new branch lengths per family, and for a reversible Q of S > 32 one
+// eigensolve per handle.  All branch lengths are uploaded once, so a reversible family's bank is enqueued behind the previous
+// family's pruning without a host wait; the general (non-reversible) bank reads one norm back per family.  A refused call
+// (tl_layout) has touched neither the device nor the model.  Results equal cb_tree_likelihood's.
+int tl_run(cb_tl_model_s &m, const TlCall &c, double *kernel_ms) {
+  TlLayout L;
+  int rc = tl_layout(m.S, m.S1, m.reversible, c, L);
   if (rc != CB_OK) return rc;
-  // one counts-free handle for all families and calls: a single "site" whose buckets are the (category, node) pairs of a family --
-  // t[c][v] = rate_c x length_v, the layout of P -- with capacity for the largest family met so far; S > 32: the model's
-  // eigensolve once.  (Round 5 made, waited for and destroyed a handle per family at S <= 32: 2 of a call's 14 ms.)
-  if (!m.hl || max_bank > m.cap_bank) {
-    if (m.hl) cb_destroy(m.hl);
-    m.hl = nullptr;
-    m.eigh_done = false;
-    m.tables_done = false;   // (the new handle's decomposition: the same solver on the same matrix, but not a promise kept here)
-    std::vector<double> t0(max_bank, 0.0);
-    if ((rc = cb_create(device, S, 1, (int)max_bank, CB_F64, t0.data(), nullptr, CB_EXPM_ONLY, &m.hl)) != CB_OK) return rc;
-    if ((rc = cb_set_stream(m.hl, nullptr, 0)) != CB_OK) return rc;
-    m.cap_bank = max_bank;
+  HIP_TRY(hipSetDevice(m.device));
+  if ((rc = tl_model_reserve(m, L)) != CB_OK) return rc;
+  CbDevBufs bufs;
+  TlDev d;
+  if ((rc = tl_upload_inputs(bufs, c, L, m.S1 > 0, d)) != CB_OK) return rc;
+  if ((rc = tl_model_handle(m, L)) != CB_OK) return rc;   // (behind the uploads: its creation enqueues copies of its own)
+  TlTimer timer(kernel_ms != nullptr);
+  if ((rc = timer.start()) != CB_OK) return rc;
+  if ((rc = tl_upload_times(bufs, L, d)) != CB_OK) return rc;
+  for (int f = 0; f < c.n_fam && rc == CB_OK; ++f) {
+    const TlDev df = tl_family_view(d, L, f);
+    if ((rc = tl_family_bank(m, L, f, df)) != CB_OK) break;
+    const bool timed = timer.family_begin();   // the pruning time of this family
+    CbSpectral sp;   // factored: what the family's bank left on the handle, and the model's tables of it
+    if (L.factored && ((rc = cb_internal_spectral(m.hl, &sp)) != CB_OK || (rc = tl_leaf_tables(m, sp)) != CB_OK)) break;
+    rc = tl_prune(m, L.fam[f], df, sp);
+    if (timed) timer.family_end();
   }
-  cb_handle hl = m.hl;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double ms_total = 0.0, ms_prune = 0.0;
-  std::vector<hipEvent_t> evm;   // one "bank done" marker per family when timing
-  if (kernel_ms) {
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipStreamSynchronize(0));   // the timed region starts with resident inputs
-    HIP_TRY(hipEventRecord(ev0, 0));
-  }
-  // branch lengths x category rates of ALL families, uploaded once (S > 32: a family's bank then starts behind the
-  // previous family's pruning on the stream without the host waiting for it)
-  std::vector<size_t> off_t(n_fam + 1, 0);
-  for (int f = 0; f < n_fam; ++f)
-    off_t[f + 1] = off_t[f] + (factored ? (size_t)std::max(fam[f].n_int, 1) : (size_t)n_cats[f] * n_nodes[f]);
-  std::vector<double> t_all(off_t[n_fam], 0.0), t_node(factored ? off_n[n_fam] : 0);
-  std::vector<int> slot_all(factored ? off_n[n_fam] : 0);
-  for (int f = 0; f < n_fam; ++f) {
-    const TlFamily &F = fam[f];
-    const double *len = length + off_n[f], *cr = cat_rate + off_k[f];
-    if (factored) {   // (one category at S > 64: tl_prepare)
-      for (int v = 0; v < F.n_nodes; ++v) {
-        const double tv = v == F.root ? 0.0 : cr[0] * len[v];
-        t_node[off_n[f] + v] = tv;
-        slot_all[off_n[f] + v] = F.slot[v];
-        if (F.slot[v] >= 0) t_all[off_t[f] + F.slot[v]] = tv;
-      }
-      continue;
-    }
-    for (int c = 0; c < F.n_cats; ++c)
-      for (int v = 0; v < F.n_nodes; ++v) t_all[off_t[f] + (size_t)c * F.n_nodes + v] = v == F.root ? 0.0 : cr[c] * len[v];
-  }
-  const double *dt_all = d.up(t_all.data(), t_all.size(), rc);
-  const double *dt_node = factored ? d.up(t_node.data(), t_node.size(), rc) : nullptr;
-  const int *dslot = factored ? d.up(slot_all.data(), slot_all.size(), rc) : nullptr;
-  if (rc != CB_OK) return rc;
-  for (int f = 0; f < n_fam && rc == CB_OK; ++f) {
-    const TlFamily &F = fam[f];
-    const double *t = t_all.data() + off_t[f];
-    // ---- transition bank expm(rate_c * length_v * Q), [cat][node][S][S], by the bank's own expm kernels
-    if ((rc = cb_internal_set_times(hl, t, (int)(off_t[f + 1] - off_t[f]), dt_all + off_t[f])) != CB_OK) break;
-    rc = cb_internal_expm_bank(hl, dQ, dpi, CB_PTR_DEVICE | CB_NO_SYNC | (large && m.eigh_done && dpi ? CB_REUSE_EIGH : 0), dP);
-    if (rc == CB_OK) m.eigh_done = true;
-    if (rc != CB_OK) break;
-    // pruning time of this family: a marker pair around its launches (both or neither)
-    hipEvent_t em = nullptr, ep = nullptr;
-    const bool timed = kernel_ms && hipEventCreate(&em) == hipSuccess && hipEventCreate(&ep) == hipSuccess;
-    if (timed) (void)hipEventRecord(em, 0);
-    const int NU = S > 64 ? (F.n_units + 31) / 32 * 32 : F.n_units;
-    TlFactored fx;
-    if (factored) {
-      CbSpectral sp;
-      if ((rc = cb_internal_spectral(hl, &sp)) != CB_OK) break;
-      const int nJ = S + (S1 > 0 ? 2 * S1 : 0) + 1;
-      if (!m.tables_done) {   // once per model, behind its eigensolve on the stream
-        if (!m.dTU && (hipMalloc((void **)&m.dTU, (size_t)nJ * sp.LD * sizeof(double)) != hipSuccess ||
-                       hipMalloc((void **)&m.dTA, (size_t)nJ * sp.LD * sizeof(double)) != hipSuccess)) {
-          (void)hipGetLastError();
-          rc = fail(CB_ENOMEM, "cb_tree_likelihood: device allocation failed");
-          break;
-        }
-        hipLaunchKernelGGL(tl_tables_kernel, dim3(nJ), dim3(256), 0, 0, S, S1, sp.LD, nJ, sp.U, sp.A, sp.dsq, m.dTU, m.dTA);
-        m.tables_done = true;
-      }
-      fx.slot = dslot + off_n[f]; fx.tnode = dt_node + off_n[f]; fx.U = sp.U; fx.lam = sp.lam; fx.dsq = sp.dsq; fx.sigma = sp.sigma;
-      fx.TU = m.dTU; fx.TA = m.dTA; fx.LD = sp.LD;
-    }
-    rc = tl_prune(S, S1, F, dP, F.n_nodes, dproot, duc + off_u[f], dca + off_c[f], dcb ? dcb + off_c[f] : nullptr,
-                  dlev + off_n[f], dcp + off_n[f] + f, dci + off_n[f], dmsg, dll + off_u[f], NU, fx);
-    if (timed) {
-      (void)hipEventRecord(ep, 0);
-      evm.push_back(em);
-      evm.push_back(ep);
-    } else {
-      if (em) (void)hipEventDestroy(em);
-      if (ep) (void)hipEventDestroy(ep);
-    }
-  }
-  if (kernel_ms) {
-    float ms = 0.f;
-    hipError_t e = hipEventRecord(ev1, 0);
-    if (e == hipSuccess) e = hipEventSynchronize(ev1);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
-    ms_total = ms;
-    for (size_t i = 0; i + 1 < evm.size(); i += 2) {
-      float mp = 0.f;
-      if (hipEventElapsedTime(&mp, evm[i], evm[i + 1]) == hipSuccess) ms_prune += mp;
-    }
-    for (hipEvent_t ev : evm) (void)hipEventDestroy(ev);
-    kernel_ms[0] = ms_total;
-    kernel_ms[1] = ms_prune;
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
-    if (e != hipSuccess && rc == CB_OK) rc = fail(CB_EHIP, "cb_tree_likelihood: %s", hipGetErrorString(e));
-  }
-  if (rc != CB_OK) return rc;
+  if ((rc = timer.finish(kernel_ms, rc)) != CB_OK) return rc;
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(ll, dll, off_u[n_fam] * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(c.ll, d.dll, L.off_u[c.n_fam] * sizeof(double), hipMemcpyDeviceToHost));
   return CB_OK;
 }
+}  // namespace
 
 extern "C" int cb_tl_model_destroy(cb_tl_model_s *m) {
   if (!m) return CB_OK;
@@ -385,18 +296,14 @@ extern "C" int cb_tl_model_create(int device, int S, int S1, const double *Q, co
   if (device < 0 || device >= ndev) return fail(CB_EINVAL, "cb_tree_likelihood: device %d of %d", device, ndev);
   HIP_TRY(hipSetDevice(device));
   cb_tl_model_s *m = new cb_tl_model_s;
-  m->device = device; m->S = S; m->S1 = S1;
+  m->device = device; m->S = S; m->S1 = S1; m->reversible = pi_rev != nullptr;
   const size_t SS = (size_t)S * S;
-  m->Q.assign(Q, Q + SS);
-  if (pi_rev) m->pi_rev.assign(pi_rev, pi_rev + S);
   bool ok = hipMalloc((void **)&m->dproot, S * sizeof(double)) == hipSuccess &&
             hipMemcpy(m->dproot, pi_root, S * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (ok) {
+  if (ok)
     ok = hipMalloc((void **)&m->dQ, SS * sizeof(double)) == hipSuccess && hipMemcpy(m->dQ, Q, SS * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && pi_rev)
-      ok = hipMalloc((void **)&m->dpi, S * sizeof(double)) == hipSuccess && hipMemcpy(m->dpi, pi_rev, S * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    m->Lrep = 1;
-  }
+  if (ok && pi_rev)
+    ok = hipMalloc((void **)&m->dpi, S * sizeof(double)) == hipSuccess && hipMemcpy(m->dpi, pi_rev, S * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
     cb_tl_model_destroy(m);
@@ -410,25 +317,24 @@ extern "C" int cb_tl_model_run(cb_tl_model_s *m, int n_fam, const int *n_nodes, 
                                const double *length, const int *n_cats, const double *cat_rate, const int *n_units,
                                const int *unit_cat, const int8_t *code_a, const int8_t *code_b, double *ll, double *kernel_ms) {
   if (!m) return fail(CB_EINVAL, "cb_tl_model_run: NULL model");
-  return tl_run(*m, n_fam, n_nodes, postorder, parent, length, n_cats, cat_rate, n_units, unit_cat, code_a, code_b, ll, kernel_ms);
+  const TlCall c{n_fam, n_nodes, postorder, parent, length, n_cats, cat_rate, n_units, unit_cat, code_a, code_b, ll};
+  const int rc = tl_check_call(m->S, m->S1, true, c);
+  return rc != CB_OK ? rc : tl_run(*m, c, kernel_ms);
 }
 
-// MANY families under ONE model in one call (the reference maps families over a process pool,
-// evaluation/_likelihood.py:474-600 / utils.py:59-67): a model made for the call (cb_tl_model_create / _run / _destroy).
+// MANY families under ONE model made for the call (cb_tl_model_create / tl_run / cb_tl_model_destroy); what needs no device
+// to refuse is refused before the model is made
 extern "C" int cb_tree_likelihood_batch(int device, int S, int S1, const double *Q, const double *pi_rev,
                                         const double *pi_root, int n_fam, const int *n_nodes, const int *postorder,
                                         const int *parent, const double *length, const int *n_cats,
                                         const double *cat_rate, const int *n_units, const int *unit_cat,
                                         const int8_t *code_a, const int8_t *code_b, double *ll, double *kernel_ms) {
-  if (!Q || !pi_root || !n_nodes || !postorder || !parent || !length || !n_cats || !cat_rate || !n_units || !unit_cat ||
-      !code_a || !ll)
-    return fail(CB_EINVAL, "cb_tree_likelihood: NULL argument");
-  if (n_fam < 1) return fail(CB_EINVAL, "cb_tree_likelihood: bad sizes (S = %d, families = %d)", S, n_fam);
-  if (S1 > 0 && !code_b) return fail(CB_EINVAL, "cb_tree_likelihood: pair model needs S = S1 * S1 and code_b");
-  cb_tl_model_s *m = nullptr;
-  int rc = cb_tl_model_create(device, S, S1, Q, pi_rev, pi_root, &m);
+  const TlCall c{n_fam, n_nodes, postorder, parent, length, n_cats, cat_rate, n_units, unit_cat, code_a, code_b, ll};
+  int rc = tl_check_call(S, S1, Q && pi_root, c);
   if (rc != CB_OK) return rc;
-  rc = tl_run(*m, n_fam, n_nodes, postorder, parent, length, n_cats, cat_rate, n_units, unit_cat, code_a, code_b, ll, kernel_ms);
+  cb_tl_model_s *m = nullptr;
+  if ((rc = cb_tl_model_create(device, S, S1, Q, pi_rev, pi_root, &m)) != CB_OK) return rc;
+  rc = tl_run(*m, c, kernel_ms);
   cb_tl_model_destroy(m);
   return rc;
 }

@@ -198,6 +198,58 @@ def test_resident_models_give_the_per_call_results_family_after_family():
             m1.log_likelihoods([tree], [np.zeros((9, 2), dtype=np.int8)], [np.zeros((9, 2), dtype=np.int8)], [np.ones(2)])
 
 
+def test_resident_model_survives_refused_calls():
+    """A refused call leaves a resident model as it was, on the timed path too: family A (9 leaves) evaluated before and after
+    a refusal, and again after family B (40 leaves) has made the buffers and the expm handle grow, gives the same bits every
+    time -- those of a model made for the call."""
+    from cherryml_amd.evaluation import LikelihoodModel, tree_likelihood_batch
+    z = load_golden("likelihood.npz")
+    rng = np.random.default_rng(311)
+    pi2, Q2 = _random_pair_model(rng)
+
+    def tree_without_zero_branches(n_leaves):   # (a leaf at distance 0 in another state: probability 0, NaN in log space)
+        while True:
+            tree, names = _random_tree(rng, n_leaves)
+            if all(tree.parent(v)[1] > 0 for v in tree.nodes() if not tree.is_root(v)):
+                return tree, [list(tree.nodes()).index(v) for v in names]
+    tree_a, leaves_a = tree_without_zero_branches(9)
+    tree_b, leaves_b = tree_without_zero_branches(40)
+
+    def codes(tree, leaves, n_units):
+        out = np.full((tree.num_nodes(), n_units), -1, dtype=np.int8)
+        out[leaves] = rng.integers(-1, 20, (len(leaves), n_units))
+        return out
+
+    for Q, pi, pairs, units_a, units_b, rates_a in [(z["wag"], z["pi_wag"], False, 8, 11, [0.5, 2.0, 1.0, 0.5, 0.5, 2.0, 1.0, 2.0]),
+                                                    (Q2, pi2, True, 5, 7, [1.0] * 5)]:
+        a_a, a_b = codes(tree_a, leaves_a, units_a), (codes(tree_a, leaves_a, units_a) if pairs else None)
+        b_a, b_b = codes(tree_b, leaves_b, units_b), (codes(tree_b, leaves_b, units_b) if pairs else None)
+        rates_b = [1.0] * units_b if pairs else list(rng.choice([0.25, 1.0, 3.0, 4.0], size=units_b))
+        wrap = lambda x: None if x is None else [x]   # noqa: E731
+        want = tree_likelihood_batch([tree_a], [a_a], wrap(a_b), Q, pi, [rates_a], alphabet_size=20)[0]
+        assert np.isfinite(want).all()
+        with LikelihoodModel(Q, pi, pairs=pairs, alphabet_size=20) as m:
+            def eval_a():
+                prof = {}
+                got = m.log_likelihoods([tree_a], [a_a], wrap(a_b), [rates_a], profile=prof)[0]
+                assert prof["kernel_ms"] > 0
+                return got
+            first = eval_a()
+            assert np.array_equal(first, want)
+            if pairs:
+                with pytest.raises(NotImplementedError, match="one rate category"):
+                    m.log_likelihoods([tree_a], [a_a], [a_b], [[1.0, 1.0, 2.0, 1.0, 1.0]], profile={})
+            else:
+                bad = a_a.copy()
+                bad[leaves_a[0], 3] = 20
+                with pytest.raises(ValueError, match="state code out of range"):
+                    m.log_likelihoods([tree_a], [bad], None, [rates_a], profile={})
+            assert np.array_equal(eval_a(), first)
+            got_b = m.log_likelihoods([tree_b], [b_a], wrap(b_b), [rates_b], profile={})[0]
+            assert got_b.shape == (units_b,) and np.isfinite(got_b).all()
+            assert np.array_equal(eval_a(), first)
+
+
 def test_likelihood_small_alphabet_pairs_and_general_S():
     """S1 = 4 (16 pair states, lane-group kernel with pair observations) and S1 = 9 (81 states, MFMA kernel,
     S not a multiple of 4 or 16)."""
