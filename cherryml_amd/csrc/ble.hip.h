@@ -76,6 +76,104 @@ __global__ __launch_bounds__(256) void ble_branch_lengths_kernel(
   }
 }
 
+// ble_branch_lengths_kernel for ALL pairs of the n sequences of one family (the distance pass of neighbour joining):
+// index[i][j] = index[j][i] = what that kernel returns for the cherry (seqs[i], seqs[j]), index[i][i] = -1.  Nothing is
+// materialised per pair: the rows of seqs [n][L] are read in place.  A pair with no site observed in both sequences sums to
+// 0.0 on both sides of every step (`0 > 0` is false: low = mid + 1) and ends at T - 1, as in ble_branch_lengths_kernel.
+// The bank it reads is the SYMMETRISED one, sym[t][r][x][y] = logP[t][r][x][y] + logP[t][r][y][x] (ble_symmetrise_kernel, once
+// per call): one gather per site and grid point where ble_branch_lengths_kernel makes two and adds them -- the same value bit
+// for bit, so the two kernels agree bit for bit (their sums run in the same order).
+// The upper triangle is cut into BLE_PW_TILE x BLE_PW_TILE tiles (bi, bj >= bi); row bi (nb - bi tiles) and row nb - 1 - bi
+// (bi + 1 tiles) share one line of nb + 1 workgroups of the grid [nb + 1][(nb + 1) / 2], so no linear pair number is decoded.
+// The four waves of a workgroup take the tile's rows in turn, one wave per pair at a time, lanes over sites.  What a lane
+// keeps: the rate base of its first BLE_PW_HOIST sites (once per wave), row i's codes folded into it (once per row), the bank
+// offset of the pair (once per pair) -- a bisection step is then 2 BLE_PW_HOIST independent gathers.  Every bound below is
+// wave-uniform: a wave reaches every wave_sum with all its lanes and leaves as a whole.
+__global__ __launch_bounds__(256) void ble_symmetrise_kernel(int S, size_t n_mats, const double *__restrict__ logP, double *__restrict__ sym) {
+  const size_t SS = (size_t)S * S, e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_mats * SS) return;
+  const size_t m = e / SS, xy = e % SS, x = xy / S, y = xy % S;
+  sym[e] = logP[e] + logP[m * SS + y * S + x];
+}
+constexpr int BLE_PW_TILE = 8;
+constexpr int BLE_PW_HOIST = 8;   // x 64 lanes = 512 sites in registers; longer alignments take the plain loop for the rest
+__global__ __launch_bounds__(256) void ble_pairwise_kernel(int S, int T, int R, int n, int L, int nb, const double *__restrict__ sym,
+                                                           const int8_t *__restrict__ seqs, const int *__restrict__ site_to_rate,
+                                                           int *__restrict__ index) {
+  int bi = blockIdx.y, bj = bi + (int)blockIdx.x;
+  if ((int)blockIdx.x >= nb - bi) {   // the second part of the line: row nb - 1 - bi
+    if (nb - 1 - bi == bi) return;    // (nb odd, the middle row: it has no partner)
+    bj = (nb - 1 - bi) + ((int)blockIdx.x - (nb - bi));
+    bi = nb - 1 - bi;
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i0 = bi * BLE_PW_TILE, j0 = bj * BLE_PW_TILE;
+  const size_t SS = (size_t)S * S, RSS = (size_t)R * SS;
+  int rb[BLE_PW_HOIST];   // site -> offset of its rate's S x S block, -1 past the end of the alignment
+#pragma unroll
+  for (int k = 0; k < BLE_PW_HOIST; ++k) {
+    const int s = lane + 64 * k;
+    rb[k] = s < L ? site_to_rate[s] * (int)SS : -1;
+  }
+  for (int r = wave; r < BLE_PW_TILE; r += 4) {
+    const int i = i0 + r;
+    if (i >= n) break;
+    const int8_t *x = seqs + (size_t)i * L;
+    int bx[BLE_PW_HOIST];   // rate base + x * S (-1: unobserved in row i, or no such site)
+#pragma unroll
+    for (int k = 0; k < BLE_PW_HOIST; ++k) {
+      const int xi = rb[k] >= 0 ? x[lane + 64 * k] : -1;
+      bx[k] = xi >= 0 ? rb[k] + xi * S : -1;
+    }
+    if (bi == bj && lane == 0) index[(size_t)i * n + i] = -1;
+    for (int c = bi == bj ? r + 1 : 0; c < BLE_PW_TILE; ++c) {
+      const int j = j0 + c;
+      if (j >= n) break;
+      const int8_t *y = seqs + (size_t)j * L;
+      int oxy[BLE_PW_HOIST];
+#pragma unroll
+      for (int k = 0; k < BLE_PW_HOIST; ++k) {
+        const int yi = bx[k] >= 0 ? y[lane + 64 * k] : -1;
+        oxy[k] = yi >= 0 ? bx[k] + yi : -1;
+      }
+      int low = 0, high = T - 1;
+      while (low < high) {
+        const int mid = low + (high - low) / 2;
+        const double *Pm = sym + (size_t)mid * RSS;
+        double a = 0.0, b = 0.0;
+        double va[BLE_PW_HOIST], vb[BLE_PW_HOIST];
+#pragma unroll
+        for (int k = 0; k < BLE_PW_HOIST; ++k) {
+          const int o = oxy[k] < 0 ? 0 : oxy[k];   // (an unobserved site reads entry 0 and adds nothing)
+          va[k] = Pm[o];
+          vb[k] = Pm[RSS + o];
+        }
+#pragma unroll
+        for (int k = 0; k < BLE_PW_HOIST; ++k)
+          if (oxy[k] >= 0) {
+            a += va[k];
+            b += vb[k];
+          }
+        for (int s = lane + 64 * BLE_PW_HOIST; s < L; s += 64) {
+          const int xi = x[s], yi = y[s];
+          if (xi < 0 || yi < 0) continue;
+          const double *M = Pm + (size_t)site_to_rate[s] * SS;
+          a += M[xi * S + yi];
+          b += M[RSS + xi * S + yi];
+        }
+        a = wave_sum(a);
+        b = wave_sum(b);
+        if (a > b) high = mid;
+        else low = mid + 1;
+      }
+      if (lane == 0) {   // the two mirrored entries
+        index[(size_t)i * n + j] = low;
+        index[(size_t)j * n + i] = low;
+      }
+    }
+  }
+}
+
 // out[s] = rate category maximising prior[r] + sum_cherries (logP[len(c)][r][x][y] + logP[..][y][x]).
 // cxT / cyT are the SITE-major copies [L][n] of the cherries, so that the lanes (consecutive
 // cherries of one site) read consecutive bytes.

@@ -63,6 +63,64 @@ extern "C" int cb_ble_branch_lengths(int device, int S, int T, int R, const doub
   return CB_OK;
 }
 
+// get_branch_lengths (:60-103) for all pairs of one family's sequences: the distance pass of neighbour joining.  Everything is
+// validated on the host before any device work; the device holds the bank and its symmetrised copy, seqs [n][L], the rate
+// indices and index [n][n].
+extern "C" int cb_ble_pairwise(int device, int S, int T, int R, const double *logP, const int8_t *seqs, int n, int L,
+                               const int *site_to_rate, int *index, double *kernel_ms) {
+  if (!logP || !seqs || !site_to_rate || !index) return fail(CB_EINVAL, "cb_ble_pairwise: NULL argument");
+  if (n < 2) return fail(CB_EINVAL, "cb_ble_pairwise: n = %d sequences (at least 2)", n);
+  if (L < 1) return fail(CB_EINVAL, "cb_ble_pairwise: L = %d sites (at least 1)", L);
+  if (S < 2 || S > 127) return fail(CB_EINVAL, "cb_ble_pairwise: S = %d states (2 to 127)", S);
+  if (T < 1 || R < 1) return fail(CB_EINVAL, "cb_ble_pairwise: T = %d grid points, R = %d rate categories (at least 1)", T, R);
+  if ((size_t)R * S * S > (size_t)INT32_MAX) return fail(CB_EINVAL, "cb_ble_pairwise: R = %d rate categories: the bank offsets pass 2^31", R);
+  const int nb = (n + BLE_PW_TILE - 1) / BLE_PW_TILE;
+  if ((nb + 1) / 2 > 65535) return fail(CB_EINVAL, "cb_ble_pairwise: n = %d sequences are more than one launch takes", n);
+  for (int i = 0; i < n; ++i)
+    for (int s = 0; s < L; ++s) {
+      const int v = seqs[(size_t)i * L + s];
+      if (v >= S || v < -1) return fail(CB_EINVAL, "cb_ble_pairwise: state code %d out of range (sequence %d, site %d)", v, i, s);
+    }
+  for (int s = 0; s < L; ++s)
+    if (site_to_rate[s] < 0 || site_to_rate[s] >= R)
+      return fail(CB_EINVAL, "cb_ble_pairwise: rate index %d out of range (site %d)", site_to_rate[s], s);
+  const int ndev = cb_device_count();
+  if (ndev <= 0) return fail(CB_EHIP, "cb_ble_pairwise: no HIP device visible");
+  if (device < 0 || device >= ndev) return fail(CB_EINVAL, "cb_ble_pairwise: device %d out of range", device);
+  HIP_TRY(hipSetDevice(device));
+  int rc = CB_OK;
+  CbDevBufs d;
+  const double *dP = d.up(logP, (size_t)T * R * S * S, rc);
+  const int8_t *dq = d.up(seqs, (size_t)n * L, rc);
+  const int *ds = d.up(site_to_rate, L, rc);
+  int *dout = d.up<int>(nullptr, (size_t)n * n, rc);
+  const size_t n_bank = (size_t)T * R * S * S;
+  double *dsym = d.up<double>(nullptr, n_bank, rc);
+  if (rc != CB_OK) return rc;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  if (kernel_ms) {
+    HIP_TRY(hipEventCreate(&ev0));
+    HIP_TRY(hipEventCreate(&ev1));
+    HIP_TRY(hipStreamSynchronize(0));  // uploads done: the timed region starts with resident inputs
+    HIP_TRY(hipEventRecord(ev0, 0));
+  }
+  hipLaunchKernelGGL(ble_symmetrise_kernel, dim3((unsigned)((n_bank + 255) / 256)), dim3(256), 0, 0, S, (size_t)T * R, dP, dsym);
+  hipLaunchKernelGGL(ble_pairwise_kernel, dim3(nb + 1, (nb + 1) / 2), dim3(256), 0, 0, S, T, R, n, L, nb, (const double *)dsym, dq, ds,
+                     dout);
+  if (kernel_ms) {
+    float ms = 0.f;
+    HIP_TRY(hipEventRecord(ev1, 0));
+    HIP_TRY(hipEventSynchronize(ev1));
+    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+    *kernel_ms = ms;
+    (void)hipEventDestroy(ev0);
+    (void)hipEventDestroy(ev1);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(index, dout, (size_t)n * n * sizeof(int), hipMemcpyDeviceToHost));
+  return CB_OK;
+}
+
 extern "C" int cb_ble_site_rates(int device, int S, int T, int R, const double *logP, const int8_t *cx,
                                  const int8_t *cy, int n, int L, const int *lengths_index, const double *priors,
                                  int *rate_index) {

@@ -1,12 +1,15 @@
 """FastCherries: branch-length / site-rate estimation on the GPU (log-transition bank, the
 two bisection passes, their coordinate ascent) and, around it, the reference's seeded divide-and-conquer
-cherry pairing (host) and tree / site-rate files (`fast_cherries`, `fast_cherries_family`)."""
+cherry pairing (host) and tree / site-rate files (`fast_cherries`, `fast_cherries_family`).  Full trees: the same bisection
+for all pairs of sequences on the GPU (`pairwise_branch_lengths`) and neighbour joining on the host (`neighbor_joining`,
+`nj_tree_family`, the stage `nj_trees`)."""
 from ._ble import (  # noqa: F401
     BleBank,
     branch_lengths,
     compute_log_transition_matrices,
     estimate_branch_lengths_and_site_rates,
     estimate_branch_lengths_and_site_rates_batch,
+    pairwise_branch_lengths,
     rate_priors,
     site_rates,
 )
@@ -19,3 +22,4 @@ from ._fast_cherries import (  # noqa: F401,E402
     get_weights_for_initial_site_rates,
     rate_categories_ble,
 )
+from ._nj import neighbor_joining, nj_distance_indices, nj_tree_family, nj_trees  # noqa: F401,E402

@@ -68,6 +68,32 @@ def branch_lengths(cx, cy, log_transition_matrices, site_to_rate_index, device: 
     return out
 
 
+def pairwise_branch_lengths(seqs, log_transition_matrices, site_to_rate_index, device: int = 0,
+                            profile: Optional[dict] = None) -> np.ndarray:
+    """`get_branch_lengths` (:60-103) for ALL pairs of the sequences `seqs` [n, L] (`cb_ble_pairwise`): [n, n] int32,
+    `out[i, j] == out[j, i]` the grid index `branch_lengths(seqs[[i]], seqs[[j]], ...)` returns, -1 on the diagonal.  A pair
+    with no site observed in both sequences gets T - 1, as `branch_lengths` gives it.  The pairs are never materialised: the
+    device holds the bank, its symmetrised copy, the n L sequence bytes and the n^2 indices.  `profile` (a dict) receives
+    `kernel_ms` (GPU time of the symmetrising and the pairwise kernel, HIP events)."""
+    import ctypes
+    seqs, logP = _i8(seqs), _f64(log_transition_matrices)
+    if seqs.ndim != 2 or logP.ndim != 4 or logP.shape[2] != logP.shape[3]:
+        raise ValueError("the sequences must be one [n, L] array and the bank [T, R, S, S]")
+    T, R, S, _ = logP.shape
+    n, L = seqs.shape
+    s2r = np.ascontiguousarray(site_to_rate_index, dtype=np.int32)
+    if s2r.shape != (L,):
+        raise ValueError("site_to_rate_index must hold one rate index per site")
+    out = np.zeros((n, n), dtype=np.int32)
+    ms = ctypes.c_double(0.0)
+    rc = _lib.load().cb_ble_pairwise(device, S, T, R, logP.ctypes.data, seqs.ctypes.data, n, L, s2r.ctypes.data,
+                                     out.ctypes.data, ctypes.addressof(ms) if profile is not None else None)
+    _lib.check(rc, "cb_ble_pairwise")
+    if profile is not None:
+        profile["kernel_ms"] = ms.value
+    return out
+
+
 def site_rates(cx, cy, log_transition_matrices, lengths_index, priors, device: int = 0) -> np.ndarray:
     """`get_site_rates` (:105-144): rate-category index of every site."""
     cx, cy, logP = _shapes(cx, cy, log_transition_matrices)

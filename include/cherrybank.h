@@ -431,6 +431,17 @@ int cb_ble_bank_run(cb_ble_bank bank, const int8_t *cx, const int8_t *cy, int n,
 int cb_ble_bank_destroy(cb_ble_bank bank);
 int cb_site_rate_gather(int device, int S, int R, int n, int L, const double *tens, const int8_t *cx,
                         const int8_t *cy, const double *log_prior, int *best);
+/* get_branch_lengths (branch_length_estimation.cpp:60-103) applied to ALL pairs of one family's sequences -- the distance
+ * pass of neighbour joining.  seqs [n][L] int8 (state index, -1 = gap / unknown), site_to_rate [L] (into the bank's R
+ * categories); out: index [n][n], index[i][j] = index[j][i] = the grid index that bisection returns for the cherry
+ * (seqs[i], seqs[j]), -1 on the diagonal.  A pair with no site observed in both sequences gets T - 1 (both sums are 0 at
+ * every step and `>` keeps the upper half), as cb_ble_branch_lengths gives it.  Nothing is materialised per pair: the device
+ * holds the bank, its symmetrised copy logP[x][y] + logP[y][x] (made once per call: one gather per site and grid point, the same
+ * value bit for bit), n L bytes of sequences and the n^2 indices.  Every argument is validated on the host before any device work
+ * (CB_EINVAL: NULL pointer, n < 2, L < 1, S outside [2, 127], a state code >= S or < -1, a rate index outside [0, R)); no
+ * device visible: CB_EHIP.  kernel_ms (may be NULL): GPU time of the two kernels, inputs already resident, by HIP events. */
+int cb_ble_pairwise(int device, int S, int T, int R, const double *logP, const int8_t *seqs, int n, int L,
+                    const int *site_to_rate, int *index, double *kernel_ms);
 
 /* ---- held-out log-likelihood of ONE family under one model (tail of SURVEY 8f #4) ---------------
  * Replaces the per-(node, site) python loops of cherryml/evaluation/_likelihood.py:47-327
