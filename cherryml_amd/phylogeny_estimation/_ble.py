@@ -61,6 +61,8 @@ def branch_lengths(cx, cy, log_transition_matrices, site_to_rate_index, device: 
     T, R, S, _ = logP.shape
     n, L = cx.shape
     s2r = np.ascontiguousarray(site_to_rate_index, dtype=np.int32)
+    if s2r.shape != (L,):
+        raise ValueError("site_to_rate_index must hold one rate index per site")
     out = np.zeros(n, dtype=np.int32)
     rc = _lib.load().cb_ble_branch_lengths(device, S, T, R, logP.ctypes.data, cx.ctypes.data, cy.ctypes.data, n, L,
                                            s2r.ctypes.data, out.ctypes.data)
@@ -101,6 +103,10 @@ def site_rates(cx, cy, log_transition_matrices, lengths_index, priors, device: i
     n, L = cx.shape
     li = np.ascontiguousarray(lengths_index, dtype=np.int32)
     pr = _f64(priors)
+    if li.shape != (n,):
+        raise ValueError("lengths_index must hold one grid index per cherry")
+    if pr.shape != (R,):
+        raise ValueError("priors must hold one log prior per rate category")
     out = np.zeros(L, dtype=np.int32)
     rc = _lib.load().cb_ble_site_rates(device, S, T, R, logP.ctypes.data, cx.ctypes.data, cy.ctypes.data, n, L,
                                        li.ctypes.data, pr.ctypes.data, out.ctypes.data)

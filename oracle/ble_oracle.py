@@ -45,7 +45,7 @@ def initial_site_rates(all_seqs: np.ndarray, weights, S: int) -> np.ndarray:
     non_missing = counts.sum(axis=1)
     total = ((non_missing[:, None] - counts) * counts).sum(axis=1)
     order = sorted(range(L), key=lambda j: (int(total[j]), j))
-    w = [int(round(x * L)) for x in weights]
+    w = [int(np.floor(abs(x * L) + 0.5) * np.sign(x * L)) for x in weights]   # std::round (:50): halves away from zero
     out = np.zeros(L, dtype=np.int32)
     rc = 0
     for i in range(L):
