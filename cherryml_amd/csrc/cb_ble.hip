@@ -1,7 +1,9 @@
 // libcherrybank: FastCherries branch lengths / site rates.
+// The host arithmetic (priors, initial bins, transposes, size checks, batch offsets) is ble_layout.h; here: the device.
 #include "cb_internal.hip.h"
 #include "common.hip.h"
 #include "ble.hip.h"
+#include "ble_layout.h"
 
 // ----------------------------------------------------------------- FastCherries BLE (8f #3)
 extern "C" int cb_ble_log_bank(int device, int S, int T, int R, const double *Q, const double *pi,
@@ -27,17 +29,61 @@ extern "C" int cb_ble_log_bank(int device, int S, int T, int R, const double *Q,
 namespace {
 std::vector<int8_t> ble_transposed(const int8_t *c, int n, int L) {
   std::vector<int8_t> t((size_t)n * L);
-  for (int i = 0; i < n; ++i)
-    for (int s = 0; s < L; ++s) t[(size_t)s * n + i] = c[(size_t)i * L + s];
+  ble_transpose(c, n, L, t.data());
   return t;
 }
-int ble_check(int device, int S, int T, int R, int n, int L, const int8_t *cx, const int8_t *cy) {
-  if (S < 2 || S > 127 || T < 1 || R < 1 || n < 1 || L < 1) return fail(CB_EINVAL, "ble: bad sizes");
+// the one device check of every entry; `who` heads the refusal
+int ble_device(const char *who, int device) {
   const int ndev = cb_device_count();
-  if (ndev <= 0) return fail(CB_EHIP, "ble: no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(CB_EINVAL, "ble: device %d out of range", device);
-  for (size_t i = 0; i < (size_t)n * L; ++i)
-    if (cx[i] >= S || cy[i] >= S) return fail(CB_EINVAL, "ble: state code out of range");
+  if (ndev <= 0) return fail(CB_EHIP, "%s: no HIP device visible", who);
+  if (device < 0 || device >= ndev) return fail(CB_EINVAL, "%s: device %d out of range", who, device);
+  return CB_OK;
+}
+// sizes, then the device, then the codes
+int ble_check(int device, int S, int T, int R, int n, int L, const int8_t *cx, const int8_t *cy) {
+  int rc = ble_check_sizes(S, T, R, n, L);
+  if (rc == CB_OK) rc = ble_device("ble", device);
+  return rc == CB_OK ? ble_check_codes(S, n, L, cx, cy) : rc;
+}
+
+// ---- the coordinate ascent (branch_length_estimation.cpp:146-241), for every entry that runs one -----------------------------
+struct BleBankView {
+  int S, T, R;
+  const double *logP, *priors;
+};
+// one family on the device; l0 holds its lengths when the ascent returns (l1: the other buffer)
+struct BleFamilyView {
+  int n, L;
+  const int8_t *x, *y, *xT, *yT;
+  int *s2r, *l0, *l1;
+};
+void ble_launch_branch_lengths(const BleBankView &b, const BleFamilyView &f, const int *previous, int *out, int *flag) {
+  hipLaunchKernelGGL(ble_branch_lengths_kernel, dim3((f.n + 3) / 4), dim3(256), 0, 0, b.S, b.T, b.R, f.n, f.L, b.logP, f.x, f.y,
+                     (const int *)f.s2r, previous, out, flag);
+}
+// The families in lockstep: the first branch-length pass, then per round a memset of the flag words, two launches per
+// still-moving family and ONE blocking read-back of all the flags.  dflag [n_fam] on the device (a family's word is set when its
+// lengths moved), moving [n_fam] on the host (scratch), iters [n_fam] out.  A converged family is a fixed point and is left alone.
+int ble_ascent(const BleBankView &b, BleFamilyView *fam, int n_fam, int max_iters, int *dflag, int *moving, int *iters) {
+  for (int f = 0; f < n_fam; ++f) {
+    ble_launch_branch_lengths(b, fam[f], nullptr, fam[f].l0, nullptr);
+    moving[f] = 1;
+    iters[f] = 0;
+  }
+  bool any = true;
+  for (int round = 0; round < max_iters && any; ++round) {
+    HIP_TRY(hipMemsetAsync(dflag, 0, n_fam * sizeof(int), 0));
+    for (int f = 0; f < n_fam; ++f) {
+      if (!moving[f]) continue;
+      BleFamilyView &F = fam[f];
+      ble_launch_site_rates(b.S, b.T, b.R, F.n, F.L, b.logP, F.xT, F.yT, (const int *)F.l0, b.priors, F.s2r);
+      ble_launch_branch_lengths(b, F, F.l0, F.l1, dflag + f);
+      std::swap(F.l0, F.l1);
+      ++iters[f];
+    }
+    HIP_TRY(hipMemcpy(moving, dflag, n_fam * sizeof(int), hipMemcpyDeviceToHost));   // (a family left alone reads 0 again)
+    any = std::any_of(moving, moving + n_fam, [](int m) { return m != 0; });
+  }
   return CB_OK;
 }
 }  // namespace
@@ -84,11 +130,9 @@ extern "C" int cb_ble_pairwise(int device, int S, int T, int R, const double *lo
   for (int s = 0; s < L; ++s)
     if (site_to_rate[s] < 0 || site_to_rate[s] >= R)
       return fail(CB_EINVAL, "cb_ble_pairwise: rate index %d out of range (site %d)", site_to_rate[s], s);
-  const int ndev = cb_device_count();
-  if (ndev <= 0) return fail(CB_EHIP, "cb_ble_pairwise: no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(CB_EINVAL, "cb_ble_pairwise: device %d out of range", device);
+  int rc = ble_device("cb_ble_pairwise", device);
+  if (rc != CB_OK) return rc;
   HIP_TRY(hipSetDevice(device));
-  int rc = CB_OK;
   CbDevBufs d;
   const double *dP = d.up(logP, (size_t)T * R * S * S, rc);
   const int8_t *dq = d.up(seqs, (size_t)n * L, rc);
@@ -97,25 +141,12 @@ extern "C" int cb_ble_pairwise(int device, int S, int T, int R, const double *lo
   const size_t n_bank = (size_t)T * R * S * S;
   double *dsym = d.up<double>(nullptr, n_bank, rc);
   if (rc != CB_OK) return rc;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (kernel_ms) {
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipStreamSynchronize(0));  // uploads done: the timed region starts with resident inputs
-    HIP_TRY(hipEventRecord(ev0, 0));
-  }
+  CbKernelTimer timer(kernel_ms != nullptr);
+  if ((rc = timer.begin(true)) != CB_OK) return rc;
   hipLaunchKernelGGL(ble_symmetrise_kernel, dim3((unsigned)((n_bank + 255) / 256)), dim3(256), 0, 0, S, (size_t)T * R, dP, dsym);
   hipLaunchKernelGGL(ble_pairwise_kernel, dim3(nb + 1, (nb + 1) / 2), dim3(256), 0, 0, S, T, R, n, L, nb, (const double *)dsym, dq, ds,
                      dout);
-  if (kernel_ms) {
-    float ms = 0.f;
-    HIP_TRY(hipEventRecord(ev1, 0));
-    HIP_TRY(hipEventSynchronize(ev1));
-    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-    *kernel_ms = ms;
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
-  }
+  if ((rc = timer.end(kernel_ms)) != CB_OK) return rc;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(index, dout, (size_t)n * n * sizeof(int), hipMemcpyDeviceToHost));
   return CB_OK;
@@ -130,8 +161,8 @@ extern "C" int cb_ble_site_rates(int device, int S, int T, int R, const double *
   for (int i = 0; i < n; ++i)
     if (lengths_index[i] < 0 || lengths_index[i] >= T) return fail(CB_EINVAL, "cb_ble_site_rates: length index out of range");
   HIP_TRY(hipSetDevice(device));
-  CbDevBufs d;
   const std::vector<int8_t> xT = ble_transposed(cx, n, L), yT = ble_transposed(cy, n, L);
+  CbDevBufs d;
   const double *dP = d.up(logP, (size_t)T * R * S * S, rc), *dpr = d.up(priors, R, rc);
   const int8_t *dxT = d.up(xT.data(), (size_t)n * L, rc), *dyT = d.up(yT.data(), (size_t)n * L, rc);
   const int *dl = d.up(lengths_index, n, rc);
@@ -141,35 +172,6 @@ extern "C" int cb_ble_site_rates(int device, int S, int T, int R, const double *
   ble_launch_site_rates(S, T, R, n, L, dP, dxT, dyT, dl, dpr, dout);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(rate_index, dout, L * sizeof(int), hipMemcpyDeviceToHost));
-  return CB_OK;
-}
-
-// initial site-rate bins (branch_length_estimation.cpp:10-58): sites ordered by the number of
-// differing sequence pairs (ties: site index); the i-th site of that order gets category rc,
-// rc advancing while i >= round(weights[rc] * L)
-static int ble_initial_bins(const int8_t *all_seqs, int n_seqs, int L, int S, int R, const double *weights, int *s2r) {
-  std::vector<long long> cnt((size_t)L * S, 0);
-  for (int i = 0; i < n_seqs; ++i)
-    for (int j = 0; j < L; ++j) {
-      const int v = all_seqs[(size_t)i * L + j];
-      if (v >= S) return fail(CB_EINVAL, "cb_ble: state code out of range");
-      if (v >= 0) cnt[(size_t)j * S + v] += 1;
-    }
-  std::vector<std::pair<long long, int>> order(L);
-  for (int j = 0; j < L; ++j) {
-    long long non_missing = 0, total = 0;
-    for (int k = 0; k < S; ++k) non_missing += cnt[(size_t)j * S + k];
-    for (int k = 0; k < S; ++k) total += (non_missing - cnt[(size_t)j * S + k]) * cnt[(size_t)j * S + k];
-    order[j] = {total, j};
-  }
-  std::sort(order.begin(), order.end());
-  std::vector<long long> w(R);
-  for (int r = 0; r < R; ++r) w[r] = (long long)std::llround(weights[r] * L);
-  int cat = 0;
-  for (int i = 0; i < L; ++i) {
-    if (cat < R && i >= w[cat]) ++cat;
-    s2r[order[i].second] = cat < R ? cat : R - 1;
-  }
   return CB_OK;
 }
 
@@ -183,54 +185,25 @@ extern "C" int cb_ble(int device, int S, int T, int R, const double *logP, const
   if (n_seqs < 1 || max_iters < 0) return fail(CB_EINVAL, "cb_ble: bad sizes");
   std::vector<int> s2r(L, 0);
   if ((rc = ble_initial_bins(all_seqs, n_seqs, L, S, R, weights, s2r.data())) != CB_OK) return rc;
-  std::vector<double> priors(R);
-  for (int r = 0; r < R; ++r) priors[r] = 2 * std::log(rates[r]) - 3 * rates[r];   // :199-203
-  HIP_TRY(hipSetDevice(device));
-  CbDevBufs d;
-  const double *dP = d.up(logP, (size_t)T * R * S * S, rc), *dpr = d.up(priors.data(), R, rc);
+  const std::vector<double> priors = ble_priors(rates, R);
   const std::vector<int8_t> xT = ble_transposed(cx, n, L), yT = ble_transposed(cy, n, L);
-  const int8_t *dx = d.up(cx, (size_t)n * L, rc), *dy = d.up(cy, (size_t)n * L, rc);
-  const int8_t *dxT = d.up(xT.data(), (size_t)n * L, rc), *dyT = d.up(yT.data(), (size_t)n * L, rc);
-  int *ds = d.up(s2r.data(), L, rc);
-  int *dl0 = d.up<int>(nullptr, n, rc), *dl1 = d.up<int>(nullptr, n, rc), *dflag = d.up<int>(nullptr, 1, rc);
+  HIP_TRY(hipSetDevice(device));
+  CbDevBufs d;   // (after every vector it uploads)
+  const size_t nc = (size_t)n * L;   // (braces: the uploads in the order written)
+  const BleBankView bank{S, T, R, d.up(logP, (size_t)T * R * S * S, rc), d.up(priors.data(), R, rc)};
+  BleFamilyView fam{n, L, d.up(cx, nc, rc), d.up(cy, nc, rc), d.up(xT.data(), nc, rc), d.up(yT.data(), nc, rc),
+                    d.up(s2r.data(), L, rc), d.up<int>(nullptr, n, rc), d.up<int>(nullptr, n, rc)};
+  int *dflag = d.up<int>(nullptr, 1, rc);
   if (rc != CB_OK) return rc;
-  const dim3 gb((n + 3) / 4), gs((L + 3) / 4), blk(256);
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (kernel_ms) {
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipStreamSynchronize(0));  // uploads done: the timed region starts with resident inputs
-    HIP_TRY(hipEventRecord(ev0, 0));
-  }
-  hipLaunchKernelGGL(ble_branch_lengths_kernel, gb, blk, 0, 0, S, T, R, n, L, dP, dx, dy, (const int *)ds,
-                     (const int *)nullptr, dl0, (int *)nullptr);
-  bool match = false;
-  int iters = 0;
-  while (!match && max_iters) {
-    ++iters;
-    HIP_TRY(hipMemsetAsync(dflag, 0, sizeof(int), 0));
-    ble_launch_site_rates(S, T, R, n, L, dP, dxT, dyT, (const int *)dl0, dpr, ds);
-    hipLaunchKernelGGL(ble_branch_lengths_kernel, gb, blk, 0, 0, S, T, R, n, L, dP, dx, dy, (const int *)ds,
-                       (const int *)dl0, dl1, dflag);
-    int flag = 0;
-    HIP_TRY(hipMemcpy(&flag, dflag, sizeof flag, hipMemcpyDeviceToHost));
-    match = flag == 0;
-    std::swap(dl0, dl1);
-    --max_iters;
-  }
-  if (kernel_ms) {
-    float ms = 0.f;
-    HIP_TRY(hipEventRecord(ev1, 0));
-    HIP_TRY(hipEventSynchronize(ev1));
-    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-    *kernel_ms = ms;
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
-  }
+  CbKernelTimer timer(kernel_ms != nullptr);
+  int moving = 0, iters = 0;
+  if ((rc = timer.begin(true)) != CB_OK || (rc = ble_ascent(bank, &fam, 1, max_iters, dflag, &moving, &iters)) != CB_OK ||
+      (rc = timer.end(kernel_ms)) != CB_OK)
+    return rc;
   if (iterations) *iterations = iters;
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(lengths_index, dl0, n * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(rate_index, ds, L * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(lengths_index, fam.l0, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(rate_index, fam.s2r, L * sizeof(int), hipMemcpyDeviceToHost));
   return CB_OK;
 }
 
@@ -246,86 +219,49 @@ extern "C" int cb_ble_batch(int device, int S, int T, int R, const double *logP,
   if (!logP || !n || !L || !cx || !cy || !all_seqs || !n_seqs || !rates || !weights || !lengths_index || !rate_index)
     return fail(CB_EINVAL, "cb_ble_batch: NULL argument");
   if (n_fam < 1 || max_iters < 0) return fail(CB_EINVAL, "cb_ble_batch: bad sizes");
-  std::vector<size_t> off_c(n_fam + 1, 0), off_n(n_fam + 1, 0), off_L(n_fam + 1, 0), off_s(n_fam + 1, 0);
+  BleBatchOffsets o;
+  int rc = ble_batch_offsets(n_fam, n, L, n_seqs, o);
+  // (every n[f], L[f] is at least 1: the rest of ble_check's sizes and the device are the same for all the families)
+  if (rc == CB_OK) rc = ble_check_sizes(S, T, R, 1, 1);
+  if (rc == CB_OK) rc = ble_device("ble", device);
+  if (rc != CB_OK) return rc;
+  const size_t nc = o.off_c[n_fam], nn = o.off_n[n_fam], nL = o.off_L[n_fam];
+  std::vector<int> s2r(nL, 0);
+  std::vector<int8_t> xT(nc), yT(nc);
   for (int f = 0; f < n_fam; ++f) {
-    if (n[f] < 1 || L[f] < 1 || n_seqs[f] < 1) return fail(CB_EINVAL, "cb_ble_batch: family %d has bad sizes", f);
-    off_c[f + 1] = off_c[f] + (size_t)n[f] * L[f];
-    off_n[f + 1] = off_n[f] + n[f];
-    off_L[f + 1] = off_L[f] + L[f];
-    off_s[f + 1] = off_s[f] + (size_t)n_seqs[f] * L[f];
+    const size_t oc = o.off_c[f];
+    if ((rc = ble_check_codes(S, n[f], L[f], cx + oc, cy + oc)) != CB_OK) return rc;
+    if ((rc = ble_initial_bins(all_seqs + o.off_s[f], n_seqs[f], L[f], S, R, weights, s2r.data() + o.off_L[f])) != CB_OK) return rc;
+    ble_transpose(cx + oc, n[f], L[f], xT.data() + oc);
+    ble_transpose(cy + oc, n[f], L[f], yT.data() + oc);
   }
-  int rc = CB_OK;
-  std::vector<int> s2r(off_L[n_fam], 0);
-  std::vector<int8_t> xT(off_c[n_fam]), yT(off_c[n_fam]);
-  for (int f = 0; f < n_fam; ++f) {
-    if ((rc = ble_check(device, S, T, R, n[f], L[f], cx + off_c[f], cy + off_c[f])) != CB_OK) return rc;
-    if ((rc = ble_initial_bins(all_seqs + off_s[f], n_seqs[f], L[f], S, R, weights, s2r.data() + off_L[f])) != CB_OK) return rc;
-    for (int i = 0; i < n[f]; ++i)
-      for (int k = 0; k < L[f]; ++k) {
-        xT[off_c[f] + (size_t)k * n[f] + i] = cx[off_c[f] + (size_t)i * L[f] + k];
-        yT[off_c[f] + (size_t)k * n[f] + i] = cy[off_c[f] + (size_t)i * L[f] + k];
-      }
-  }
-  std::vector<double> priors(R);
-  for (int r = 0; r < R; ++r) priors[r] = 2 * std::log(rates[r]) - 3 * rates[r];   // :199-203
+  const std::vector<double> priors = ble_priors(rates, R);
   HIP_TRY(hipSetDevice(device));
-  CbDevBufs d;
-  const double *dP = d.up(logP, (size_t)T * R * S * S, rc), *dpr = d.up(priors.data(), R, rc);
-  const int8_t *dx = d.up(cx, off_c[n_fam], rc), *dy = d.up(cy, off_c[n_fam], rc);
-  const int8_t *dxT = d.up(xT.data(), off_c[n_fam], rc), *dyT = d.up(yT.data(), off_c[n_fam], rc);
-  int *ds = d.up(s2r.data(), off_L[n_fam], rc);
-  int *dl0 = d.up<int>(nullptr, off_n[n_fam], rc), *dl1 = d.up<int>(nullptr, off_n[n_fam], rc);
+  CbDevBufs d;   // (after every vector it uploads)
+  const BleBankView bank{S, T, R, d.up(logP, (size_t)T * R * S * S, rc), d.up(priors.data(), R, rc)};
+  const int8_t *dx = d.up(cx, nc, rc), *dy = d.up(cy, nc, rc);
+  const int8_t *dxT = d.up(xT.data(), nc, rc), *dyT = d.up(yT.data(), nc, rc);
+  int *ds = d.up(s2r.data(), nL, rc);
+  int *dl0 = d.up<int>(nullptr, nn, rc), *dl1 = d.up<int>(nullptr, nn, rc);
   int *dflag = d.up<int>(nullptr, n_fam, rc);
   if (rc != CB_OK) return rc;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (kernel_ms) {
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipStreamSynchronize(0));  // uploads done: the timed region starts with resident inputs
-    HIP_TRY(hipEventRecord(ev0, 0));
-  }
-  const dim3 blk(256);
-  // cur[f]: which of the two length buffers holds family f's current lengths
-  std::vector<int *> cur(n_fam), nxt(n_fam);
+  std::vector<BleFamilyView> fam(n_fam);
   for (int f = 0; f < n_fam; ++f) {
-    cur[f] = dl0 + off_n[f];
-    nxt[f] = dl1 + off_n[f];
-    hipLaunchKernelGGL(ble_branch_lengths_kernel, dim3((n[f] + 3) / 4), blk, 0, 0, S, T, R, n[f], L[f], dP, dx + off_c[f],
-                       dy + off_c[f], (const int *)(ds + off_L[f]), (const int *)nullptr, cur[f], (int *)nullptr);
+    const size_t oc = o.off_c[f];
+    fam[f] = {n[f], L[f], dx + oc, dy + oc, dxT + oc, dyT + oc, ds + o.off_L[f], dl0 + o.off_n[f], dl1 + o.off_n[f]};
   }
-  std::vector<int> active(n_fam), iters(n_fam, 0), flags(n_fam);
-  for (int f = 0; f < n_fam; ++f) active[f] = f;
-  for (int round = 0; round < max_iters && !active.empty(); ++round) {
-    HIP_TRY(hipMemsetAsync(dflag, 0, n_fam * sizeof(int), 0));
-    for (int f : active) {
-      ble_launch_site_rates(S, T, R, n[f], L[f], dP, dxT + off_c[f], dyT + off_c[f], (const int *)cur[f], dpr, ds + off_L[f]);
-      hipLaunchKernelGGL(ble_branch_lengths_kernel, dim3((n[f] + 3) / 4), blk, 0, 0, S, T, R, n[f], L[f], dP, dx + off_c[f],
-                         dy + off_c[f], (const int *)(ds + off_L[f]), (const int *)cur[f], nxt[f], dflag + f);
-    }
-    HIP_TRY(hipMemcpy(flags.data(), dflag, n_fam * sizeof(int), hipMemcpyDeviceToHost));
-    std::vector<int> still;
-    for (int f : active) {
-      ++iters[f];
-      std::swap(cur[f], nxt[f]);
-      if (flags[f] != 0) still.push_back(f);
-    }
-    active.swap(still);
-  }
-  if (kernel_ms) {
-    float ms = 0.f;
-    HIP_TRY(hipEventRecord(ev1, 0));
-    HIP_TRY(hipEventSynchronize(ev1));
-    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-    *kernel_ms = ms;
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
-  }
+  std::vector<int> moving(n_fam), iters(n_fam);
+  CbKernelTimer timer(kernel_ms != nullptr);
+  if ((rc = timer.begin(true)) != CB_OK ||
+      (rc = ble_ascent(bank, fam.data(), n_fam, max_iters, dflag, moving.data(), iters.data())) != CB_OK ||
+      (rc = timer.end(kernel_ms)) != CB_OK)
+    return rc;
   HIP_TRY(hipGetLastError());
   for (int f = 0; f < n_fam; ++f) {
-    HIP_TRY(hipMemcpyAsync(lengths_index + off_n[f], cur[f], n[f] * sizeof(int), hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipMemcpyAsync(lengths_index + o.off_n[f], fam[f].l0, n[f] * sizeof(int), hipMemcpyDeviceToHost, 0));
     if (iterations) iterations[f] = iters[f];
   }
-  HIP_TRY(hipMemcpyAsync(rate_index, ds, off_L[n_fam] * sizeof(int), hipMemcpyDeviceToHost, 0));
+  HIP_TRY(hipMemcpyAsync(rate_index, ds, nL * sizeof(int), hipMemcpyDeviceToHost, 0));
   HIP_TRY(hipStreamSynchronize(0));
   return CB_OK;
 }
@@ -344,7 +280,11 @@ struct cb_ble_bank_s {
   int8_t *x = nullptr, *y = nullptr, *xT = nullptr, *yT = nullptr, *seqs = nullptr;
   int *s2r = nullptr, *l0 = nullptr, *l1 = nullptr, *flags = nullptr;
   long long *totals = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  CbKernelTimer events{true};   // owns the two events a call's timer borrows
+  // host ends of a call's asynchronous copies: here, not locals of the call, so that they outlive the copies on every return path
+  std::vector<long long> h_totals;   // [cap_L], like h_s2r
+  std::vector<int> h_s2r;
+  int h_bad = 0;
 };
 
 static void ble_bank_free_ws(cb_ble_bank_s *b) {
@@ -364,27 +304,22 @@ extern "C" int cb_ble_bank_destroy(cb_ble_bank_s *b) {
   if (b->logP) (void)hipFree(b->logP);
   if (b->priors) (void)hipFree(b->priors);
   if (b->flags) (void)hipFree(b->flags);
-  if (b->ev0) (void)hipEventDestroy(b->ev0);
-  if (b->ev1) (void)hipEventDestroy(b->ev1);
-  delete b;
+  delete b;   // (and its events)
   return CB_OK;
 }
 
 extern "C" int cb_ble_bank_create(int device, int S, int T, int R, const double *logP, const double *rates, cb_ble_bank_s **out) {
   if (!logP || !rates || !out) return fail(CB_EINVAL, "cb_ble_bank_create: NULL argument");
   if (S < 2 || S > 127 || T < 1 || R < 1) return fail(CB_EINVAL, "cb_ble_bank_create: bad sizes");
-  const int ndev = cb_device_count();
-  if (ndev <= 0) return fail(CB_EHIP, "cb_ble_bank_create: no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(CB_EINVAL, "cb_ble_bank_create: device %d out of range", device);
+  const int rc = ble_device("cb_ble_bank_create", device);
+  if (rc != CB_OK) return rc;
   HIP_TRY(hipSetDevice(device));
   cb_ble_bank_s *b = new cb_ble_bank_s;
   b->device = device; b->S = S; b->T = T; b->R = R;
-  std::vector<double> priors(R);
-  for (int r = 0; r < R; ++r) priors[r] = 2 * std::log(rates[r]) - 3 * rates[r];   // branch_length_estimation.cpp:199-203
+  const std::vector<double> priors = ble_priors(rates, R);
   const size_t nb = (size_t)T * R * S * S;
   bool ok = hipMalloc((void **)&b->logP, nb * sizeof(double)) == hipSuccess && hipMalloc((void **)&b->priors, R * sizeof(double)) == hipSuccess &&
-            hipMalloc((void **)&b->flags, 4 * sizeof(int)) == hipSuccess && hipEventCreate(&b->ev0) == hipSuccess &&
-            hipEventCreate(&b->ev1) == hipSuccess;
+            hipMalloc((void **)&b->flags, 4 * sizeof(int)) == hipSuccess && b->events.create() == CB_OK;
   ok = ok && hipMemcpy(b->logP, logP, nb * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
        hipMemcpy(b->priors, priors.data(), R * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) {
@@ -396,24 +331,10 @@ extern "C" int cb_ble_bank_create(int device, int S, int T, int R, const double 
   return CB_OK;
 }
 
-// the second half of the initial bins (branch_length_estimation.cpp:36-58) from the device's per-site totals
-static void ble_bins_from_totals(const long long *total, int L, int R, const double *weights, int *s2r) {
-  std::vector<std::pair<long long, int>> order(L);
-  for (int j = 0; j < L; ++j) order[j] = {total[j], j};
-  std::sort(order.begin(), order.end());
-  int cat = 0;
-  for (int i = 0; i < L; ++i) {
-    if (cat < R && i >= (long long)std::llround(weights[cat] * L)) ++cat;
-    s2r[order[i].second] = cat < R ? cat : R - 1;
-  }
-}
-
-extern "C" int cb_ble_bank_run(cb_ble_bank_s *b, const int8_t *cx, const int8_t *cy, int n, int L, const int8_t *all_seqs, int n_seqs,
-                               const double *weights, int max_iters, int *lengths_index, int *rate_index, int *iterations,
-                               double *kernel_ms) {
-  if (!b || !cx || !cy || !all_seqs || !weights || !lengths_index || !rate_index) return fail(CB_EINVAL, "cb_ble_bank_run: NULL argument");
-  if (n < 1 || L < 1 || n_seqs < 1 || max_iters < 0) return fail(CB_EINVAL, "cb_ble_bank_run: bad sizes");
-  HIP_TRY(hipSetDevice(b->device));
+// a call on the handle's device, its arguments checked (the entry below waits for the stream when this fails)
+static int ble_bank_run(cb_ble_bank_s *b, const int8_t *cx, const int8_t *cy, int n, int L, const int8_t *all_seqs, int n_seqs,
+                        const double *weights, int max_iters, int *lengths_index, int *rate_index, int *iterations,
+                        double *kernel_ms) {
   const int S = b->S, T = b->T, R = b->R;
   const size_t nc = (size_t)n * L, ns = (size_t)n_seqs * L;
   if (nc > b->cap_c || ns > b->cap_s || (size_t)n > b->cap_n || (size_t)L > b->cap_L) {   // (grow: everything anew, sizes kept as maxima)
@@ -430,6 +351,8 @@ extern "C" int cb_ble_bank_run(cb_ble_bank_s *b, const int8_t *cx, const int8_t 
       return fail(CB_ENOMEM, "cb_ble_bank_run: device allocation failed");
     }
     b->cap_c = cc; b->cap_s = cs; b->cap_n = cn; b->cap_L = cl;
+    b->h_totals = std::vector<long long>(cl);
+    b->h_s2r = std::vector<int>(cl);
   }
   HIP_TRY(hipMemsetAsync(b->flags, 0, 4 * sizeof(int), 0));
   HIP_TRY(hipMemcpyAsync(b->seqs, all_seqs, ns, hipMemcpyHostToDevice, 0));
@@ -440,47 +363,37 @@ extern "C" int cb_ble_bank_run(cb_ble_bank_s *b, const int8_t *cx, const int8_t 
   const dim3 tg((L + 63) / 64, (n + 63) / 64);
   hipLaunchKernelGGL(ble_transpose_check_kernel, tg, dim3(256), 0, 0, n, L, S, b->x, b->xT, b->flags + 1);
   hipLaunchKernelGGL(ble_transpose_check_kernel, tg, dim3(256), 0, 0, n, L, S, b->y, b->yT, b->flags + 1);
-  std::vector<long long> totals(L);
-  int bad = 0;
-  HIP_TRY(hipMemcpyAsync(totals.data(), b->totals, L * sizeof(long long), hipMemcpyDeviceToHost, 0));
-  HIP_TRY(hipMemcpyAsync(&bad, b->flags + 1, sizeof bad, hipMemcpyDeviceToHost, 0));
+  HIP_TRY(hipMemcpyAsync(b->h_totals.data(), b->totals, L * sizeof(long long), hipMemcpyDeviceToHost, 0));
+  HIP_TRY(hipMemcpyAsync(&b->h_bad, b->flags + 1, sizeof(int), hipMemcpyDeviceToHost, 0));
   HIP_TRY(hipStreamSynchronize(0));
-  if (bad) return fail(CB_EINVAL, "cb_ble_bank_run: state code out of range");
-  std::vector<int> s2r(L);
-  ble_bins_from_totals(totals.data(), L, R, weights, s2r.data());
-  HIP_TRY(hipMemcpyAsync(b->s2r, s2r.data(), L * sizeof(int), hipMemcpyHostToDevice, 0));
-  const dim3 gb((n + 3) / 4), blk(256);
-  if (kernel_ms) HIP_TRY(hipEventRecord(b->ev0, 0));
-  int *dl0 = b->l0, *dl1 = b->l1, *dflag = b->flags;
-  hipLaunchKernelGGL(ble_branch_lengths_kernel, gb, blk, 0, 0, S, T, R, n, L, (const double *)b->logP, (const int8_t *)b->x, (const int8_t *)b->y,
-                     (const int *)b->s2r, (const int *)nullptr, dl0, (int *)nullptr);
-  bool match = false;
-  int iters = 0;
-  while (!match && max_iters) {
-    ++iters;
-    HIP_TRY(hipMemsetAsync(dflag, 0, sizeof(int), 0));
-    ble_launch_site_rates(S, T, R, n, L, b->logP, b->xT, b->yT, (const int *)dl0, b->priors, b->s2r);
-    hipLaunchKernelGGL(ble_branch_lengths_kernel, gb, blk, 0, 0, S, T, R, n, L, (const double *)b->logP, (const int8_t *)b->x,
-                       (const int8_t *)b->y, (const int *)b->s2r, (const int *)dl0, dl1, dflag);
-    int flag = 0;
-    HIP_TRY(hipMemcpy(&flag, dflag, sizeof flag, hipMemcpyDeviceToHost));
-    match = flag == 0;
-    std::swap(dl0, dl1);
-    --max_iters;
-  }
-  if (kernel_ms) {
-    float ms = 0.f;
-    HIP_TRY(hipEventRecord(b->ev1, 0));
-    HIP_TRY(hipEventSynchronize(b->ev1));
-    HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-    *kernel_ms = ms;
-  }
+  if (b->h_bad) return fail(CB_EINVAL, "cb_ble_bank_run: state code out of range");
+  ble_bins_from_totals(b->h_totals.data(), L, R, weights, b->h_s2r.data());
+  HIP_TRY(hipMemcpyAsync(b->s2r, b->h_s2r.data(), L * sizeof(int), hipMemcpyHostToDevice, 0));
+  const BleBankView bank{S, T, R, b->logP, b->priors};
+  BleFamilyView fam{n, L, b->x, b->y, b->xT, b->yT, b->s2r, b->l0, b->l1};
+  CbKernelTimer timer(kernel_ms != nullptr, b->events.ev0, b->events.ev1);
+  int rc, moving = 0, iters = 0;   // (flag word 0: the ascent's; word 1: the bad-code flag read above)
+  if ((rc = timer.begin(false)) != CB_OK || (rc = ble_ascent(bank, &fam, 1, max_iters, b->flags, &moving, &iters)) != CB_OK ||
+      (rc = timer.end(kernel_ms)) != CB_OK)
+    return rc;
   if (iterations) *iterations = iters;
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(lengths_index, dl0, n * sizeof(int), hipMemcpyDeviceToHost, 0));
+  HIP_TRY(hipMemcpyAsync(lengths_index, fam.l0, n * sizeof(int), hipMemcpyDeviceToHost, 0));
   HIP_TRY(hipMemcpyAsync(rate_index, b->s2r, L * sizeof(int), hipMemcpyDeviceToHost, 0));
   HIP_TRY(hipStreamSynchronize(0));
   return CB_OK;
+}
+
+extern "C" int cb_ble_bank_run(cb_ble_bank_s *b, const int8_t *cx, const int8_t *cy, int n, int L, const int8_t *all_seqs, int n_seqs,
+                               const double *weights, int max_iters, int *lengths_index, int *rate_index, int *iterations,
+                               double *kernel_ms) {
+  if (!b || !cx || !cy || !all_seqs || !weights || !lengths_index || !rate_index) return fail(CB_EINVAL, "cb_ble_bank_run: NULL argument");
+  if (n < 1 || L < 1 || n_seqs < 1 || max_iters < 0) return fail(CB_EINVAL, "cb_ble_bank_run: bad sizes");
+  HIP_TRY(hipSetDevice(b->device));
+  const int rc = ble_bank_run(b, cx, cy, n, L, all_seqs, n_seqs, weights, max_iters, lengths_index, rate_index, iterations, kernel_ms);
+  // the caller's arrays are the other ends of asynchronous copies: none is in flight when a failed call returns
+  if (rc != CB_OK) (void)hipStreamSynchronize(0);
+  return rc;
 }
 
 extern "C" int cb_site_rate_gather(int device, int S, int R, int n, int L, const double *tens, const int8_t *cx,

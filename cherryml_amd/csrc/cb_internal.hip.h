@@ -1,6 +1,6 @@
 // Shared by the translation units of libcherrybank: error reporting and small host-side helpers.
-// (cherrybank.hip: handle, bank entry points, trainers; cb_bank_fused.hip: the one-launch bank kernel; cb_counting.hip;
-// cb_ble.hip; cb_likelihood.hip; cb_host_io.hip.)
+// (cherrybank.hip: handle, bank entry points, trainers; cb_bank_fused.hip: the one-launch bank kernel; cb_tbasis.hip: the bank in a
+// time basis; cb_counting.hip; cb_ble.hip; cb_likelihood.hip; cb_host_io.hip; cb_simulate.hip; cb_em.hip.)
 #pragma once
 #include "../../include/cherrybank.h"
 
@@ -103,6 +103,7 @@ static inline const char *cb_test_hook(const char *name) {
 }
 
 // device buffers of one call of the per-family entry points (uploaded on the default stream, freed on return)
+// the rule: a host buffer `up` reads is declared BEFORE the CbDevBufs, whose hipFree waits for the upload on every return path
 struct CbDevBufs {
   std::vector<void *> ptrs;
   ~CbDevBufs() {
@@ -121,5 +122,46 @@ struct CbDevBufs {
     if (host && count && hipMemcpyAsync(q, host, count * sizeof(T), hipMemcpyHostToDevice, 0) != hipSuccess)
       rc = fail(CB_EHIP, "upload failed");
     return static_cast<T *>(q);
+  }
+};
+
+// the kernel time of a call on the default stream (kernel_ms); off: every member does nothing.  Owns its two events, or borrows
+// the two a resident handle keeps.  (hidden: no symbol of the library)
+struct __attribute__((visibility("hidden"))) CbKernelTimer {
+  const bool on, owned;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  explicit CbKernelTimer(bool on_) : on(on_), owned(true) {}
+  CbKernelTimer(bool on_, hipEvent_t b0, hipEvent_t b1) : on(on_), owned(false), ev0(b0), ev1(b1) {}
+  CbKernelTimer(const CbKernelTimer &) = delete;
+  ~CbKernelTimer() { drop(); }
+  void drop() {
+    if (owned && ev0) (void)hipEventDestroy(ev0);
+    if (owned && ev1) (void)hipEventDestroy(ev1);
+    ev0 = ev1 = nullptr;
+  }
+  // (a resident handle: once, for the borrowers of its calls)
+  int create() {
+    HIP_TRY(hipEventCreate(&ev0));
+    HIP_TRY(hipEventCreate(&ev1));
+    return CB_OK;
+  }
+  // sync_first: the timed region starts with resident inputs (the uploads of the call are done)
+  int begin(bool sync_first) {
+    if (!on) return CB_OK;
+    const int rc = owned ? create() : CB_OK;
+    if (rc != CB_OK) return rc;
+    if (sync_first) HIP_TRY(hipStreamSynchronize(0));
+    HIP_TRY(hipEventRecord(ev0, 0));
+    return CB_OK;
+  }
+  int end(double *ms) {
+    if (!on) return CB_OK;
+    float t = 0.f;
+    HIP_TRY(hipEventRecord(ev1, 0));
+    HIP_TRY(hipEventSynchronize(ev1));
+    HIP_TRY(hipEventElapsedTime(&t, ev0, ev1));
+    *ms = t;
+    drop();
+    return CB_OK;
   }
 };

@@ -32,7 +32,8 @@ step.  With the fixed seeds below, on the CPU: no item of any group is undecided
   tie banks, the steps that are no tie                    1.1e-04
   gather, the best total against the second best          1.1e-03
   ascents: (37,91) 6.1e-06 in 8 iterations, (70,2049) 4.2e-07 in 11, (2050,40) 1.3e-07 in 2, (5,600) 7.8e-06 in 4 (R = 4) and
-  1.4e-05 in 5 (R = 8); stopped after 0 or 1 iterations 8.9e-06; the six-site family of the rounding test 3.4e-03
+  1.4e-05 in 5 (R = 8); stopped after 0 or 1 iterations 8.9e-06; the six-site family of the rounding test 3.4e-03;
+  the small batch (3,5) (4,33) (65,64) (7,513): 1, 2, 7 and 5 iterations, 8.6e-07 (cut off after 4: 1, 2, 4, 4)
 Needs an MI355X."""
 import os
 import sys
@@ -405,3 +406,55 @@ def test_resident_entry_finds_a_bad_code_in_the_last_tile(banks):
         prof = {}
         got = resident.estimate(*case[:4], 50, profile=prof)
         check_ascent(got, prof, case, grid, rates, "after the refused family")
+
+
+# ------------------------------------------------------------------------------------------------ 8. one ascent behind three entries
+@pytest.mark.parametrize("max_iters", [0, 1, 50])
+def test_the_three_entries_agree_on_one_family(banks, max_iters):
+    """cb_ble, the resident entry and a batch of one run the same loop: the same lengths, rates and iteration count"""
+    from cherryml_amd.phylogeny_estimation import (BleBank, estimate_branch_lengths_and_site_rates,
+                                                   estimate_branch_lengths_and_site_rates_batch)
+    logP, grid, rates = banks("lg4")
+    with BleBank(logP, grid, rates) as resident:
+        for shape in ((37, 91), (70, 2049)):
+            case = ascent_case("lg4", shape, max_iters)
+            cx, cy, seqs, w = case[:4]
+            per_call, one, batch = {}, {}, {}
+            a = estimate_branch_lengths_and_site_rates(cx, cy, seqs, logP, grid, rates, w, max_iters, profile=per_call)
+            b = resident.estimate(cx, cy, seqs, w, max_iters, profile=one)
+            c = estimate_branch_lengths_and_site_rates_batch([(cx, cy, seqs)], logP, grid, rates, w, max_iters, profile=batch)
+            assert len(c) == 1 and batch["iterations"] == [per_call["iterations"]] and one["iterations"] == per_call["iterations"]
+            for got in (b, c[0]):
+                assert np.array_equal(got[0], a[0]) and np.array_equal(got[1], a[1]), shape
+            check_ascent(a, per_call, case, grid, rates, f"three entries, max_iters = {max_iters}, {shape}")
+
+
+SMALL_BATCH = [(3, 5), (4, 33), (65, 64), (7, 513)]
+
+
+@pytest.mark.parametrize("max_iters", [4, 50])
+def test_a_batch_of_small_families_that_stop_at_different_rounds(banks, max_iters):
+    """Four families in lockstep that leave the loop at different rounds.  With these seeds the restatement takes 1, 2, 7 and 5
+    iterations; max_iters = 4 cuts the last two off while they are still moving.  Each family's lengths, rates and iteration
+    count are those of its own cb_ble call, with the kernel time asked for and without."""
+    from cherryml_amd.phylogeny_estimation import (estimate_branch_lengths_and_site_rates,
+                                                   estimate_branch_lengths_and_site_rates_batch)
+    logP, grid, rates = banks("lg4")
+    cases = [ascent_case("lg4", s, max_iters) for s in SMALL_BATCH]
+    # the precondition, on the CPU: the iteration counts differ, and the cut families would have gone on
+    assert [ascent_case("lg4", s, 50)[6] for s in SMALL_BATCH] == [1, 2, 7, 5]
+    assert [c[6] for c in cases] == ([1, 2, 4, 4] if max_iters == 4 else [1, 2, 7, 5])
+    assert all(c[7] > UNDECIDED for c in cases)
+    w = cases[0][3]
+    prof = {}
+    timed = estimate_branch_lengths_and_site_rates_batch([c[:3] for c in cases], logP, grid, rates, w, max_iters, profile=prof)
+    plain = estimate_branch_lengths_and_site_rates_batch([c[:3] for c in cases], logP, grid, rates, w, max_iters)
+    assert len(timed) == len(plain) == 4 and prof["kernel_ms"] > 0.0
+    for k, (shape, case) in enumerate(zip(SMALL_BATCH, cases)):
+        own = {}
+        want = estimate_branch_lengths_and_site_rates(*case[:3], logP, grid, rates, w, max_iters, profile=own)
+        bare = estimate_branch_lengths_and_site_rates(*case[:3], logP, grid, rates, w, max_iters)
+        for got in (timed[k], plain[k], bare):
+            assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), shape
+        assert prof["iterations"][k] == own["iterations"], shape
+        check_ascent(want, own, case, grid, rates, f"small batch, max_iters = {max_iters}, {shape}")
