@@ -1,6 +1,6 @@
 // Shared by the translation units of libcherrybank: error reporting and small host-side helpers.
 // (cherrybank.hip: handle, bank entry points, trainers; cb_bank_fused.hip: the one-launch bank kernel; cb_tbasis.hip: the bank in a
-// time basis; cb_counting.hip; cb_ble.hip; cb_likelihood.hip; cb_host_io.hip; cb_simulate.hip; cb_em.hip.)
+// time basis; cb_counting.hip; cb_ble.hip; cb_likelihood.hip; cb_host_io.hip; cb_simulate.hip; cb_em.hip; cb_bl.hip.)
 #pragma once
 #include "../../include/cherrybank.h"
 

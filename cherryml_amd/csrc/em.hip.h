@@ -19,7 +19,7 @@
 // The task lists are fixed at handle creation, so two E-steps on the same input give bitwise-equal counts.
 #pragma once
 #include "common.hip.h"
-#include "tl_group.hip.h"
+#include "em_shared.hip.h"
 
 // inside pass: tl_group_body with P_v of unit u = bank[qb[v * n_cats + unit_cat[u]]]
 __global__ __launch_bounds__(64) void em_up_kernel(TlArgs a, const int *__restrict__ qb, int n_cats) {
@@ -27,17 +27,6 @@ __global__ __launch_bounds__(64) void em_up_kernel(TlArgs a, const int *__restri
     return a.P + ((size_t)qb[(size_t)v * n_cats + a.unit_cat[uu]] * a.S + r) * a.S;
   });
 }
-
-struct EmDownArgs {
-  int S, n_units, root, n_blocks, n_cats;
-  const int *level_nodes;            // internal non-root nodes of one depth
-  const int *parent, *child_ptr, *child_idx;
-  const int *qb, *unit_cat;
-  const double *P;                   // [B][S][S]
-  const double *pi_root;             // [S]
-  const double *msg;                 // upward messages [node][unit][S]
-  double *U;                         // outside messages [node][unit][S] (internal non-root nodes)
-};
 
 // grid = nodes of the depth x unit blocks, 64 threads; lane = (unit in wave, state): state a while x is formed, b for U_v[b]
 __global__ __launch_bounds__(64) void em_down_kernel(EmDownArgs a) {

@@ -1,0 +1,260 @@
+"""Maximum-likelihood branch lengths on fixed trees: EM over the internal states on the GPU (csrc/bl.hip.h, the resident `cb_bl_*`
+handle).
+
+The lengths are the parameters and live on the quantisation grid of `fast_cherries` / `nj_trees`; the topology, the rate matrix,
+the root distribution and the site rates are fixed.  One round is the inside and outside passes at the current lengths and, for
+every edge independently, the grid point that maximises the expected complete-data log-likelihood -- an exact EM step, so no
+round lowers a family's likelihood.  `BranchLengthFitter` is the handle, `ml_branch_lengths` the stage on tree / MSA / site-rate
+directories, `nj_ml_trees` the tree estimator `nj_trees` + `ml_branch_lengths`.
+
+Out of scope: site-rate re-estimation, topology moves, a continuous (off-grid) optimiser, S > 32."""
+import ctypes
+import os
+import time
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from .. import _lib
+from ..caching import cached_computation
+from ..io._tree import Tree, read_tree, write_tree
+from ._fast_cherries import quantization_points_ble
+
+DEFAULT_MAX_BANK_BYTES = 4 << 30   # banks (P and log P) of the families of one handle, at most
+
+
+class BranchLengthFitter:
+    """Branch-length EM resident on one GPU: trees, leaf codes, site-rate categories and each family's bank of
+    expm(grid[tau] rate_c Q) and its logarithm are built once (`cb_bl_create`); `round()` is one EM step for all families.
+
+    trees: `io.Tree`s (their lengths are snapped to the grid: the start); leaf_codes: per family an int8 array
+    [n_nodes, n_sites] with rows in `tree.nodes()` order (-1 = gap; only leaf rows are read); site_rates: per family [n_sites],
+    finite and > 0; grid: the T >= 2 grid points (increasing); Q [S, S], pi_root [S], 2 <= S <= 32.  A context manager;
+    `close()` frees the handle."""
+
+    def __init__(self, trees: Sequence, leaf_codes: Sequence[np.ndarray], site_rates: Sequence, grid: Sequence[float], Q, pi_root,
+                 device: Optional[int] = None):
+        from ..counting._stage import _device_index
+        from ..evaluation._likelihood import _tree_arrays
+        self._h = None
+        self.grid = np.ascontiguousarray(np.asarray(grid, dtype=np.float64).reshape(-1))
+        self.Q = np.ascontiguousarray(Q, dtype=np.float64)
+        self.pi_root = np.ascontiguousarray(pi_root, dtype=np.float64).reshape(-1)
+        S = self.Q.shape[0]
+        if self.Q.shape != (S, S) or self.pi_root.shape != (S,):
+            raise ValueError(f"BranchLengthFitter: Q must be square and pi_root of its size: {self.Q.shape}, {self.pi_root.shape}")
+        if len(trees) == 0 or len(trees) != len(leaf_codes) or len(trees) != len(site_rates):
+            raise ValueError("BranchLengthFitter: need one tree, one code array and one site-rate vector per family "
+                             "(at least one family)")
+        n_nodes, n_units, parent, length, rates, codes = [], [], [], [], [], []
+        self._nodes: List[List[str]] = []
+        for tree, c, r in zip(trees, leaf_codes, site_rates):
+            _, _, par, ln = _tree_arrays(tree)
+            c = np.ascontiguousarray(c, dtype=np.int8)
+            r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
+            if c.ndim != 2 or c.shape[0] != par.size or c.shape[1] != r.size:
+                raise ValueError("BranchLengthFitter: codes must be [n_nodes, n_sites] and site_rates [n_sites]")
+            n_nodes.append(par.size), n_units.append(r.size)
+            parent.append(par), length.append(ln), rates.append(r), codes.append(c.reshape(-1))
+            self._nodes.append(list(tree.nodes()))
+        self.S = S
+        self.n_nodes = np.array(n_nodes, dtype=np.int32)
+        self.n_units = np.array(n_units, dtype=np.int32)
+        self._args = [np.ascontiguousarray(np.concatenate(x), dtype=dt) for x, dt in
+                      ((parent, np.int32), (length, np.float64), (rates, np.float64), (codes, np.int8))]
+        self.device = _device_index() if device is None else int(device)
+        self.last_kernel_ms = (0.0, 0.0)   # (passes, M-step) of the last round
+        self._create()
+
+    def _create(self) -> None:
+        par, ln, rt, cd = self._args
+        h = ctypes.c_void_p()
+        rc = _lib.load().cb_bl_create(self.device, self.S, self.grid.size, self.grid.ctypes.data, self.Q.ctypes.data,
+                                      self.pi_root.ctypes.data, self.n_nodes.size, self.n_nodes.ctypes.data, par.ctypes.data,
+                                      ln.ctypes.data, self.n_units.ctypes.data, rt.ctypes.data, cd.ctypes.data, ctypes.byref(h))
+        _lib.check(rc, "cb_bl_create")
+        self._h = h
+
+    def _handle(self):
+        if self._h is None:
+            raise _lib.CherryBankError("BranchLengthFitter is closed")
+        return self._h
+
+    def round(self) -> Tuple[np.ndarray, np.ndarray]:
+        """One EM step -> (n_changed [n_fam], fam_ll [n_fam]): the indices the round changed and every family's log-likelihood
+        at the lengths the round STARTED from.  A family whose round changes nothing is at a fixed point and is skipped from
+        then on (0 and the same log-likelihood)."""
+        n_changed = np.zeros(self.n_nodes.size, dtype=np.int32)
+        fam_ll = np.empty(self.n_nodes.size)
+        ms = (ctypes.c_double * 2)(0.0, 0.0)
+        _lib.check(_lib.load().cb_bl_round(self._handle(), n_changed.ctypes.data, fam_ll.ctypes.data, ctypes.addressof(ms)), "cb_bl_round")
+        self.last_kernel_ms = (ms[0], ms[1])
+        return n_changed, fam_ll
+
+    def _get(self, with_ll: bool):
+        index = np.empty(int(self.n_nodes.sum()), dtype=np.int32)
+        ll = np.empty(int(self.n_units.sum())) if with_ll else None
+        fam = np.empty(self.n_nodes.size) if with_ll else None
+        rc = _lib.load().cb_bl_get(self._handle(), index.ctypes.data, ll.ctypes.data if with_ll else None,
+                                   fam.ctypes.data if with_ll else None)
+        _lib.check(rc, "cb_bl_get")
+        return index, ll, fam
+
+    def indices(self) -> List[np.ndarray]:
+        """per family the grid index of the edge above every node, rows in `tree.nodes()` order (the root: -1)"""
+        return np.split(self._get(False)[0], np.cumsum(self.n_nodes)[:-1])
+
+    def lengths(self) -> List[Dict[str, float]]:
+        """per family {node: grid[tau]} for every node but the root"""
+        return [{v: float(self.grid[t]) for v, t in zip(nodes, idx) if t >= 0} for nodes, idx in zip(self._nodes, self.indices())]
+
+    def log_likelihoods(self) -> Tuple[List[np.ndarray], np.ndarray]:
+        """(per family the log-likelihood of every site, their sums per family) at the current lengths"""
+        _, ll, fam = self._get(True)
+        return np.split(ll, np.cumsum(self.n_units)[:-1]), fam
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            _lib.load().cb_bl_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _batches(bank_bytes: Sequence[int], bound: int) -> List[List[int]]:
+    """the families in order, cut where the next family's banks would pass `bound` (a family larger than it goes alone)"""
+    out: List[List[int]] = []
+    fill = 0
+    for f, b in enumerate(bank_bytes):
+        if not out or fill + b > bound:
+            out.append([])
+            fill = 0
+        out[-1].append(f)
+        fill += b
+    return out
+
+
+@cached_computation(output_dirs=["output_tree_dir", "output_likelihood_dir"], exclude_args=["max_bank_bytes"])
+def ml_branch_lengths(tree_dir: str, msa_dir: str, site_rates_dir: str, families: List[str], rate_matrix_path: str,
+                      num_rounds: int = 10, quantization_grid_center: float = 0.03, quantization_grid_step: float = 1.1,
+                      quantization_grid_num_steps: int = 64, output_tree_dir: Optional[str] = None,
+                      output_likelihood_dir: Optional[str] = None, max_bank_bytes: int = DEFAULT_MAX_BANK_BYTES, _version="1") -> None:
+    """Refit the branch lengths of `<tree_dir>/<family>.txt` by at most `num_rounds` EM rounds under the rate matrix at the
+    family's site rates, on the grid (center, step, num_steps) of `fast_cherries` / `nj_trees`.  Per family:
+    `<output_tree_dir>/<family>.txt` (the input tree, topology, node names and their order untouched, every length a grid point),
+    `<family>.rounds` (per round `<round> <log-likelihood at its start> <indices changed>`, then `final <log-likelihood of the
+    written lengths>`; a family stops at its fixed point), `<family>.profiling`, and `<output_likelihood_dir>/<family>.txt` as
+    `nj_trees` writes it (`dp_likelihood_computation_batch` on the written trees, root distribution = the matrix's stationary
+    distribution).  All families go in one handle unless their banks would exceed `max_bank_bytes`; then they go in batches in
+    family order -- families are independent, so the results do not depend on the batching."""
+    from ..counting._host import read_msa, read_site_rates
+    from ..counting._stage import _device_index
+    from ..evaluation._likelihood import (_family_units, _stationary_distribution, dp_likelihood_computation_batch,
+                                          write_log_likelihood)
+    from ..io import read_rate_matrix
+    if output_tree_dir is None or output_likelihood_dir is None:
+        raise ValueError("output_tree_dir and output_likelihood_dir are required")
+    if _lib.load().cb_device_count() <= 0:
+        raise _lib.CherryBankError("ml_branch_lengths: no HIP device visible; the fit runs on the MI355X only (no CPU fallback)")
+    st_all = time.time()
+    for d in (output_tree_dir, output_likelihood_dir):
+        os.makedirs(d, exist_ok=True)
+    rm = read_rate_matrix(rate_matrix_path)
+    alphabet = [str(c) for c in rm.columns]
+    Q = np.ascontiguousarray(rm.to_numpy(), dtype=np.float64)
+    pi_root = _stationary_distribution(Q)
+    grid = np.array(quantization_points_ble(quantization_grid_center, quantization_grid_step, quantization_grid_num_steps))
+    device = _device_index()
+    trees, msas, rates, codes = [], [], [], []
+    for family in families:
+        tree = read_tree(os.path.join(tree_dir, family + ".txt"))
+        msa = read_msa(os.path.join(msa_dir, family + ".txt"))
+        r = np.asarray(read_site_rates(os.path.join(site_rates_dir, family + ".txt")), dtype=np.float64)
+        trees.append(tree), msas.append(msa), rates.append(r)
+        codes.append(_family_units(tree, msa, None, len(r), alphabet, False)[2])
+    bank_bytes = [2 * grid.size * np.unique(r).size * Q.size * 8 for r in rates]
+    out_trees: List[Optional[Tree]] = [None] * len(families)
+    logs: List[List[str]] = [[] for _ in families]
+    profs: List[Dict[str, float]] = [{} for _ in families]
+    for batch in _batches(bank_bytes, int(max_bank_bytes)):
+        st = time.time()
+        with BranchLengthFitter([trees[f] for f in batch], [codes[f] for f in batch], [rates[f] for f in batch], grid, Q, pi_root,
+                                device=device) as fit:
+            t_create = time.time() - st
+            live = np.ones(len(batch), dtype=bool)
+            ms_pass = ms_mstep = 0.0
+            rounds = 0
+            for rnd in range(int(num_rounds)):
+                if not live.any():
+                    break
+                n_changed, fam_ll = fit.round()
+                rounds += 1
+                ms_pass, ms_mstep = ms_pass + fit.last_kernel_ms[0], ms_mstep + fit.last_kernel_ms[1]
+                for k, f in enumerate(batch):
+                    if live[k]:
+                        logs[f].append(f"{rnd} {float(fam_ll[k])!r} {int(n_changed[k])}\n")
+                live &= n_changed > 0
+            lengths = fit.lengths()
+            _, fam_final = fit.log_likelihoods()
+        for k, f in enumerate(batch):
+            logs[f].append(f"final {float(fam_final[k])!r}\n")
+            t = Tree()
+            t.add_nodes(trees[f].nodes())
+            t.add_edges([(u, v, lengths[k][v]) for u, v, _ in trees[f].edges()])
+            out_trees[f] = t
+            profs[f] = dict(create_time=t_create / len(batch), rounds=rounds, passes_kernel_ms=ms_pass / len(batch),
+                            mstep_kernel_ms=ms_mstep / len(batch), fit_time=(time.time() - st) / len(batch))   # (shares of the batch)
+    st = time.time()
+    lls = dp_likelihood_computation_batch(out_trees, msas, [None] * len(families), [[float(x) for x in r] for r in rates], alphabet,
+                                          pi_root, Q, device=device)
+    t_ll = (time.time() - st) / max(len(families), 1)
+    t_total = (time.time() - st_all) / max(len(families), 1)
+    for f, family in enumerate(families):
+        write_tree(out_trees[f], os.path.join(output_tree_dir, family + ".txt"))
+        with open(os.path.join(output_tree_dir, family + ".rounds"), "w") as fh:
+            fh.write("".join(logs[f]))
+        write_log_likelihood(lls[f], os.path.join(output_likelihood_dir, family + ".txt"))
+        with open(os.path.join(output_tree_dir, family + ".profiling"), "w") as fh:
+            fh.write("".join(f"{k}: {v}\n" for k, v in profs[f].items()) + f"likelihood_time: {t_ll}\ntotal_time: {t_total}")
+
+
+def nj_ml_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, num_rate_categories: int, max_iters: int = 50,
+                num_processes: int = 1, num_rounds: int = 10, output_tree_dir: Optional[str] = None,
+                output_site_rates_dir: Optional[str] = None, output_likelihood_dir: Optional[str] = None, remake=False,
+                quantization_grid_center=0.03, quantization_grid_step=1.1, quantization_grid_num_steps=64, verbose=True,
+                seed=1234) -> Dict[str, str]:
+    """`nj_trees`, then `ml_branch_lengths` on its trees at its site rates and the same grid: `nj_trees`' interface plus
+    `num_rounds`, and under `functools.partial` a `tree_estimator` of the end-to-end pipelines.  Returns the output directories:
+    `output_tree_dir` / `output_likelihood_dir` hold the refitted trees and their likelihoods, `output_site_rates_dir` is
+    `nj_trees`' own.  Both stages are cached on their own; `nj_trees`, its files and its cache keys are what they are without
+    this function.  With no cache directory the three output directories are required and the neighbour-joining trees and
+    likelihoods go to their `nj_trees` subdirectories."""
+    from ..caching import get_cache_dir
+    from ._nj import nj_trees
+    nj_out = dict(output_tree_dir=None, output_site_rates_dir=output_site_rates_dir, output_likelihood_dir=None)
+    if get_cache_dir() is None:
+        if output_tree_dir is None or output_site_rates_dir is None or output_likelihood_dir is None:
+            raise ValueError("output_tree_dir, output_site_rates_dir and output_likelihood_dir are required without a cache directory")
+        nj_out.update(output_tree_dir=os.path.join(output_tree_dir, "nj_trees"),
+                      output_likelihood_dir=os.path.join(output_likelihood_dir, "nj_trees"))
+    grid_args = dict(quantization_grid_center=quantization_grid_center, quantization_grid_step=quantization_grid_step,
+                     quantization_grid_num_steps=quantization_grid_num_steps)
+    nj = nj_trees(msa_dir=msa_dir, families=families, rate_matrix_path=rate_matrix_path, num_rate_categories=num_rate_categories,
+                  max_iters=max_iters, num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, **grid_args, **nj_out)
+    nj = nj if nj is not None else nj_out
+    ml_out = dict(output_tree_dir=output_tree_dir, output_likelihood_dir=output_likelihood_dir)
+    ml = ml_branch_lengths(tree_dir=nj["output_tree_dir"], msa_dir=msa_dir, site_rates_dir=nj["output_site_rates_dir"],
+                           families=families, rate_matrix_path=rate_matrix_path, num_rounds=num_rounds, **grid_args, **ml_out)
+    ml = ml if ml is not None else ml_out
+    return dict(output_tree_dir=ml["output_tree_dir"], output_site_rates_dir=nj["output_site_rates_dir"],
+                output_likelihood_dir=ml["output_likelihood_dir"])

@@ -564,6 +564,37 @@ int cb_em_create(int device, int S, int B, const double *grid, int n_fam, const 
 int cb_em_estep(cb_em h, const double *Q, const double *pi_root, double *counts, double *ll, double *fam_ll, double *kernel_ms);
 int cb_em_destroy(cb_em h);
 
+/* ---- maximum-likelihood branch lengths on fixed trees, EM on a resident handle (S <= 32) -------------------------------------
+ * Stands in for the branch-length optimisation of the tree builders the reference calls (FastTree / PhyML): topology, Q, the root
+ * distribution and the site rates are fixed, the lengths are the parameters, and they live on the grid of T points: the edge
+ * above node v carries the index tau_v and, at a site of rate category c (the distinct rates of the family), the matrix
+ * P[tau_v][c] = expm(grid[tau_v] rate_c Q) -- the exact product of length and rate, not cb_em's second quantisation.  One round
+ * is one exact EM step over the internal states for all edges at once: inside and outside passes, then per edge
+ * tau_v' = argmax over the WHOLE grid of sum_c <E_vc, log P[tau][c]> (the lowest index among exact maxima; a term with E = 0 is 0).
+ * No round lowers a family's likelihood.
+ *
+ * cb_bl_create validates on the host before any device work -- what cb_em_create refuses (with the families laid out as there),
+ * T >= 2, a positive strictly increasing grid, site rates finite and > 0 (rate 0: log expm(0) is no bank entry), at most
+ * CB_BL_MAX_CATS distinct rates per family, a Q and pi_root cb_em_estep would refuse -- snaps the input lengths to the grid
+ * (the reference's nearest-point rule, clamped to the grid's ends) and builds each family's bank and its logarithm once.
+ * With no GPU it fails (CB_EHIP): there is no CPU path.
+ *
+ * cb_bl_round: n_changed [n_fam] the indices the round changed, fam_ll [n_fam] the log-likelihood at the lengths the round
+ *   STARTED from, kernel_ms (may be NULL) [2]: the device time of the passes and of the M-step.  A family whose round changed
+ *   nothing is at a fixed point: later rounds skip it and return 0 and the same fam_ll.
+ * cb_bl_get: index [sum n_nodes] the current indices (the root's: -1), ll [sum n_units] (may be NULL) the log-likelihood of every
+ *   site and fam_ll [n_fam] (may be NULL) their sums per family, both at the CURRENT lengths.
+ * No atomics, fixed orders: two handles on the same input give the same indices and bitwise-equal likelihoods.  One call at a
+ * time per handle. */
+#define CB_BL_MAX_CATS 64
+typedef struct cb_bl_s *cb_bl;
+int cb_bl_create(int device, int S, int T, const double *grid, const double *Q, const double *pi_root, int n_fam,
+                 const int *n_nodes, const int *parent, const double *length, const int *n_units, const double *unit_rate,
+                 const int8_t *codes, cb_bl *out);
+int cb_bl_round(cb_bl h, int *n_changed, double *fam_ll, double *kernel_ms);
+int cb_bl_get(cb_bl h, int *index, double *ll, double *fam_ll);
+int cb_bl_destroy(cb_bl h);
+
 /* ---- FastCherries' cherry pairing, host only -------------------------------------------------------------
  * divide_and_pair of phylogeny_estimation/FastCherries/pairing_algorithms.cpp:77-175 on int8 sequences
  * [n][L] (state index, -1 unknown): the seeded divide-and-conquer over Hamming distances, with the
