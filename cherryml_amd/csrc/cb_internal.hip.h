@@ -1,6 +1,6 @@
 // Shared by the translation units of libcherrybank: error reporting and small host-side helpers.
 // (cherrybank.hip: handle, bank entry points, trainers; cb_bank_fused.hip: the one-launch bank kernel; cb_tbasis.hip: the bank in a
-// time basis; cb_counting.hip; cb_ble.hip; cb_likelihood.hip; cb_host_io.hip; cb_simulate.hip; cb_em.hip; cb_bl.hip.)
+// time basis; cb_counting.hip; cb_ble.hip; cb_likelihood.hip; cb_host_io.hip; cb_simulate.hip; cb_em.hip; cb_bl.hip; cb_sr.hip.)
 #pragma once
 #include "../../include/cherrybank.h"
 
@@ -95,7 +95,8 @@ int cb_tb_launch_ew(const CbTbEwArgs &a, hipStream_t stream, hipEvent_t stop, in
 //     CB_BANK_KG, CB_BANK_TEST_NO_CLAIM, CB_PHI_Z;
 //   time basis maintenance (cherrybank.hip): CB_TB_TEST_GROWTH, CB_TB_TEST_WARN;
 //   eigensolver (train_host.hip.h, eigh_large_host.hip.h): CB_EIGH_HOST, CB_NO_HYBRID, CB_EIGH_SHORT_PLAN;
-//   counts (create_host.hip.h): CB_NO_SYM;   faults (cherrybank.hip, train_host.hip.h): CB_FAULT_INJECT.
+//   counts (create_host.hip.h): CB_NO_SYM;   faults (cherrybank.hip, train_host.hip.h): CB_FAULT_INJECT;
+//   the site-rate scan's candidate chunks (cb_sr.hip): CB_SR_MSG_BYTES.
 // (CB_DEBUG and CB_TRACE_SLOW only log; CB_BANK_STREAMS is a documented opt-in.)
 static inline const char *cb_test_hook(const char *name) {
   const char *on = getenv("CB_TEST_HOOKS");

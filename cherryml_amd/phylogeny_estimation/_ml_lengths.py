@@ -7,7 +7,7 @@ every edge independently, the grid point that maximises the expected complete-da
 round lowers a family's likelihood.  `BranchLengthFitter` is the handle, `ml_branch_lengths` the stage on tree / MSA / site-rate
 directories, `nj_ml_trees` the tree estimator `nj_trees` + `ml_branch_lengths`.
 
-Out of scope: site-rate re-estimation, topology moves, a continuous (off-grid) optimiser, S > 32."""
+Out of scope: topology moves, a continuous (off-grid) optimiser, S > 32."""
 import ctypes
 import os
 import time

@@ -595,6 +595,33 @@ int cb_bl_round(cb_bl h, int *n_changed, double *fam_ll, double *kernel_ms);
 int cb_bl_get(cb_bl h, int *index, double *ll, double *fam_ll);
 int cb_bl_destroy(cb_bl h);
 
+/* ---- the maximum-likelihood rate category of every site on fixed full trees (S <= 32) ----------------------------------------
+ * Stands in for the per-site rate categories (CAT) FastTree fits on the whole tree and the reference reads back
+ * (phylogeny_estimation/_fast_tree.py, translate_site_rates): topology, lengths, Q and the root distribution are fixed, and every
+ * site of family f is evaluated at every one of the family's n_cands[f] candidate rates -- candidate c puts
+ * expm(length_v cands[c] Q) on the edge above v, the exact product as in cb_bl_create, with no grid: the lengths need not lie
+ * on one, and the root's is ignored.  The families are laid out as for cb_bl_create / cb_em_create (codes [n_nodes][n_units], -1 = a gap, leaf rows only);
+ * cands holds the families' candidates concatenated, each family's strictly increasing, finite and > 0; current [sum n_units]
+ * (may be NULL) is every site's present candidate index or -1.
+ *
+ *   best    [sum n_units]  the candidate of highest log-likelihood; among exact maxima current[site] if it is one of them, else the
+ *                          lowest index (all candidates at -inf is such a tie).  A site with fewer than two observed leaves is
+ *                          decided from the codes, not the likelihoods: it keeps current[site] (candidate 0 where that is -1 or
+ *                          current is NULL).
+ *   best_ll [sum n_units]  the log-likelihood at `best`: the picked entry of ll_all, bit for bit.
+ *   ll_all  (may be NULL)  per family [n_cands[f]][n_units[f]], concatenated: the log-likelihood of every site at every candidate.
+ *   kernel_ms (may be NULL) [2]: the device time of the banks and of the scan with the pick, summed over the families.
+ *
+ * Everything is validated on the host before any device work (CB_EINVAL names the value): what cb_em_create refuses of the trees,
+ * lengths and codes, 1 <= n_cands[f] <= CB_SR_MAX_CANDS, the candidates, current outside [-1, n_cands[f]), a Q and pi_root
+ * cb_em_estep would refuse.  With no GPU it fails (CB_EHIP): there is no CPU path.  The call works family by family (candidates
+ * in chunks under a byte bound of its own) and frees what it allocated; no atomics, and a workgroup writes only its own tile, so
+ * a family alone and the same family among others give bitwise-equal results, as do two calls. */
+#define CB_SR_MAX_CANDS 64
+int cb_tree_site_rates(int device, int S, const double *Q, const double *pi_root, int n_fam, const int *n_nodes,
+                       const int *parent, const double *length, const int *n_units, const int8_t *codes, const int *n_cands,
+                       const double *cands, const int *current, int *best, double *best_ll, double *ll_all, double *kernel_ms);
+
 /* ---- FastCherries' cherry pairing, host only -------------------------------------------------------------
  * divide_and_pair of phylogeny_estimation/FastCherries/pairing_algorithms.cpp:77-175 on int8 sequences
  * [n][L] (state index, -1 unknown): the seeded divide-and-conquer over Hamming distances, with the
