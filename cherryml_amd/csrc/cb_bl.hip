@@ -1,8 +1,9 @@
 // libcherrybank: maximum-likelihood branch lengths on fixed trees by EM, on a resident handle (bl.hip.h; include/cherrybank.h,
-// cb_bl_*).
+// cb_bl_*), and the nearest-neighbour-interchange scan on the handle's resident messages (nni.hip.h; cb_bl_nni_scan).
 #include "cb_internal.hip.h"
 #include "common.hip.h"
 #include "bl.hip.h"
+#include "nni.hip.h"
 #include "em_host.hip.h"
 
 struct cb_bl_s {
@@ -13,6 +14,7 @@ struct cb_bl_s {
                                                                                // cat_ptr, log bank
   std::vector<int> bank_base;             // per family: its first bank entry
   std::vector<int> tau;                   // [sum n_nodes] the current indices (root: -1), the device's mirror
+  std::vector<int> parent;                // [sum n_nodes] the families' parent arrays (the host's copy: cb_bl_nni_scan validates on it)
   std::vector<char> fixed, ll_fresh;      // per family: at a fixed point; dll holds l_u at the current indices
   std::vector<double> fam_ll;             // per family: the log-likelihood at the current indices when ll_fresh
   std::vector<void *> bufs;               // every device buffer below
@@ -103,6 +105,7 @@ extern "C" int cb_bl_create(int device, int S, int T, const double *grid, const 
   h->bank_base[n_fam] = (int)entries;
   h->n_nodes_all = h->off_n[n_fam];
   h->n_units_all = h->off_u[n_fam];
+  h->parent.assign(parent, parent + h->n_nodes_all);
   // the input lengths snapped to the grid (the nearest point in ratio, clamped to its ends); the edge's bank entries
   h->tau.assign(h->n_nodes_all, -1);
   for (int f = 0; f < n_fam; ++f) {
@@ -325,5 +328,127 @@ extern "C" int cb_bl_get(cb_bl_s *h, int *index, double *ll, double *fam_ll) {
   std::fill(h->ll_fresh.begin(), h->ll_fresh.end(), 1);
   if (ll) std::copy(orig.begin(), orig.end(), ll);
   if (fam_ll) std::copy(h->fam_ll.begin(), h->fam_ll.end(), fam_ll);
+  return CB_OK;
+}
+
+namespace {
+constexpr size_t NNI_LL_BYTES = (size_t)256 << 20;   // ll'[move][unit] of one chunk of moves, at most (one move always goes)
+
+// the bound above, or the test hook CB_NNI_LL_BYTES (cb_internal.hip.h): the results do not depend on the chunking
+size_t nni_ll_bound() {
+  const char *s = cb_test_hook("CB_NNI_LL_BYTES");
+  const long long x = s ? atoll(s) : 0;
+  return x > 0 ? (size_t)x : NNI_LL_BYTES;
+}
+}  // namespace
+
+extern "C" int cb_bl_nni_scan(cb_bl_s *h, const int *n_moves, const int *moves, double *delta, double *ll_moves, double *fam_ll,
+                              double *kernel_ms) {
+  static const char *who = "cb_bl_nni_scan";
+  if (!h) return fail(CB_EINVAL, "%s: NULL handle", who);
+  if (!n_moves || !delta) return fail(CB_EINVAL, "%s: NULL argument", who);
+  // every triple, on the host, before any device work
+  const int n_fam = h->n_fam;
+  std::vector<size_t> off_m(n_fam + 1, 0), off_o(n_fam + 1, 0);
+  for (int f = 0; f < n_fam; ++f) {
+    if (n_moves[f] < 0) return fail(CB_EINVAL, "%s: family %d: n_moves = %d", who, f, n_moves[f]);
+    off_m[f + 1] = off_m[f] + n_moves[f];
+    off_o[f + 1] = off_o[f] + (size_t)n_moves[f] * h->fam[f].n_units;
+  }
+  if (off_m[n_fam] > 0 && !moves) return fail(CB_EINVAL, "%s: NULL argument", who);
+  size_t max_moves = 0, max_out = 0;
+  std::vector<int> chunk(n_fam, 0);
+  const size_t bound = nni_ll_bound();
+  for (int f = 0; f < n_fam; ++f) {
+    const EmFamHost &F = h->fam[f];
+    const int n = F.n_nodes, *par = h->parent.data() + h->off_n[f];
+    for (int m = 0; m < n_moves[f]; ++m) {
+      const int *t = moves + 3 * (off_m[f] + m);
+      const int v = t[0], c = t[1], s = t[2];
+      if (v < 0 || v >= n) return fail(CB_EINVAL, "%s: family %d move %d: v = %d (0 <= index < %d)", who, f, m, v, n);
+      if (c < 0 || c >= n) return fail(CB_EINVAL, "%s: family %d move %d: c = %d (0 <= index < %d)", who, f, m, c, n);
+      if (s < 0 || s >= n) return fail(CB_EINVAL, "%s: family %d move %d: s = %d (0 <= index < %d)", who, f, m, s, n);
+      if (v == F.root) return fail(CB_EINVAL, "%s: family %d move %d: v = %d is the root", who, f, m, v);
+      if (F.child_ptr[v] == F.child_ptr[v + 1]) return fail(CB_EINVAL, "%s: family %d move %d: v = %d is a leaf", who, f, m, v);
+      if (par[c] != v) return fail(CB_EINVAL, "%s: family %d move %d: c = %d is not a child of v = %d", who, f, m, c, v);
+      if (s == v) return fail(CB_EINVAL, "%s: family %d move %d: s = %d equals v", who, f, m, s);
+      if (par[s] != par[v])
+        return fail(CB_EINVAL, "%s: family %d move %d: s = %d is not a child of parent[v] = %d", who, f, m, s, par[v]);
+    }
+    if (n_moves[f] == 0) continue;
+    const size_t n_blocks = ((size_t)F.n_units + 64 / h->S - 1) / (64 / h->S);
+    const size_t fit = std::min(bound / ((size_t)F.n_units * sizeof(double)), (size_t)INT32_MAX / n_blocks);
+    chunk[f] = (int)std::min<size_t>(n_moves[f], std::max<size_t>(fit, 1));
+    max_moves = std::max(max_moves, (size_t)n_moves[f]);
+    max_out = std::max(max_out, (size_t)chunk[f] * F.n_units);
+  }
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.0;
+  if (max_moves > 0) {
+    HIP_TRY(hipSetDevice(h->device));
+    // the messages of the families that are scanned, at the current indices: after a round the resident ones are its start's
+    if (kernel_ms) HIP_TRY(hipEventRecord(h->ev[0], 0));
+    for (int f = 0; f < n_fam; ++f)
+      if (n_moves[f] > 0) bl_launch_passes(h, f, true);
+    HIP_TRY(hipGetLastError());
+    if (kernel_ms) {
+      float ms = 0.f;
+      HIP_TRY(hipEventRecord(h->ev[1], 0));
+      HIP_TRY(hipEventSynchronize(h->ev[1]));
+      HIP_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+      kernel_ms[0] = ms;
+    }
+    int rc = CB_OK;
+    std::vector<double> host_out(ll_moves ? max_out : 0);
+    CbDevBufs bufs;   // this call's: freed on every return path
+    int *dmoves = bufs.up<int>(nullptr, 3 * max_moves, rc);
+    double *dout = bufs.up<double>(nullptr, max_out, rc), *ddelta = bufs.up<double>(nullptr, max_moves, rc);
+    if (rc != CB_OK) return rc;
+    for (int f = 0; f < n_fam; ++f) {
+      if (n_moves[f] == 0) continue;
+      const EmFamHost &F = h->fam[f];
+      const size_t nb = h->off_c[f];
+      const int U = F.n_units, upw = 64 / h->S;
+      HIP_TRY(hipMemcpy(dmoves, moves + 3 * off_m[f], 3 * (size_t)n_moves[f] * sizeof(int), hipMemcpyHostToDevice));
+      NniArgs a{};
+      a.S = h->S; a.n_units = U; a.n_cats = F.n_cats; a.root = F.root; a.n_blocks = (U + upw - 1) / upw;
+      a.parent = h->dparent + h->off_n[f]; a.child_ptr = h->dcp + h->off_n[f] + f; a.child_idx = h->dci + h->off_n[f];
+      a.qb = h->dqb + h->off_q[f]; a.unit_cat = h->duc + h->off_u[f]; a.P = h->dP; a.pi_root = h->dpi;
+      a.msg = h->dmsg + nb * h->S; a.U = h->dU + nb * h->S; a.ll = h->dll + h->off_u[f]; a.out = dout;
+      for (int m0 = 0; m0 < n_moves[f]; m0 += chunk[f]) {
+        const int nm = std::min(chunk[f], n_moves[f] - m0);
+        a.moves = dmoves + 3 * (size_t)m0;
+        a.delta = ddelta + m0;
+        if (kernel_ms) HIP_TRY(hipEventRecord(h->ev[1], 0));
+        hipLaunchKernelGGL(nni_scan_kernel, dim3((unsigned)nm * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
+        hipLaunchKernelGGL(nni_sum_kernel, dim3((unsigned)nm), dim3(64), 0, 0, a);
+        HIP_TRY(hipGetLastError());
+        if (kernel_ms) {
+          float ms = 0.f;
+          HIP_TRY(hipEventRecord(h->ev[2], 0));
+          HIP_TRY(hipEventSynchronize(h->ev[2]));
+          HIP_TRY(hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
+          kernel_ms[1] += ms;
+        }
+        // (the next chunk writes the same buffer: stream order puts it behind this chunk's sum)
+        if (ll_moves) {   // device (category) order -> the caller's unit order
+          HIP_TRY(hipMemcpy(host_out.data(), dout, (size_t)nm * U * sizeof(double), hipMemcpyDeviceToHost));
+          for (int m = 0; m < nm; ++m) {
+            double *dst = ll_moves + off_o[f] + (size_t)(m0 + m) * U;
+            for (int k = 0; k < U; ++k) dst[F.perm[k]] = host_out[(size_t)m * U + k];
+          }
+        }
+      }
+      HIP_TRY(hipMemcpy(delta + off_m[f], ddelta, (size_t)n_moves[f] * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    // dll of the scanned families now holds l_u at the current indices -- the bits cb_bl_get's inside pass would write
+    std::vector<char> stale(n_fam);
+    for (int f = 0; f < n_fam; ++f) stale[f] = n_moves[f] > 0 && !h->ll_fresh[f];
+    rc = bl_read_ll(h, stale, nullptr);
+    if (rc != CB_OK) return rc;
+    for (int f = 0; f < n_fam; ++f)
+      if (stale[f]) h->ll_fresh[f] = 1;
+  }
+  if (fam_ll)
+    for (int f = 0; f < n_fam; ++f) fam_ll[f] = h->ll_fresh[f] ? h->fam_ll[f] : std::nan("");
   return CB_OK;
 }

@@ -4,7 +4,9 @@ cherry pairing (host) and tree / site-rate files (`fast_cherries`, `fast_cherrie
 for all pairs of sequences on the GPU (`pairwise_branch_lengths`) and neighbour joining on the host (`neighbor_joining`,
 `nj_tree_family`, the stage `nj_trees`); maximum-likelihood lengths on a fixed tree by EM on the GPU (`BranchLengthFitter`,
 the stages `ml_branch_lengths` and `nj_ml_trees`) and the maximum-likelihood rate category of every site on it
-(`tree_site_rates`, the stages `ml_site_rates`, `ml_lengths_and_site_rates` and `nj_ml_rates_trees`)."""
+(`tree_site_rates`, the stages `ml_site_rates`, `ml_lengths_and_site_rates` and `nj_ml_rates_trees`); topology search by
+nearest-neighbour interchange scored on the GPU from the fitter's resident messages (`BranchLengthFitter.nni_scan`,
+`select_nni`, `apply_nni`, the stages `ml_nni_trees` and `nj_nni_trees`)."""
 from ._ble import (  # noqa: F401
     BleBank,
     branch_lengths,
@@ -27,3 +29,4 @@ from ._fast_cherries import (  # noqa: F401,E402
 from ._nj import neighbor_joining, nj_distance_indices, nj_tree_family, nj_trees  # noqa: F401,E402
 from ._ml_lengths import BranchLengthFitter, ml_branch_lengths, nj_ml_trees  # noqa: F401,E402
 from ._site_rates import ml_lengths_and_site_rates, ml_site_rates, nj_ml_rates_trees, tree_site_rates  # noqa: F401,E402
+from ._nni import apply_nni, enumerate_nni_moves, ml_nni_trees, nj_nni_trees, select_nni  # noqa: F401,E402

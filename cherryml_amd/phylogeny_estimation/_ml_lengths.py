@@ -7,7 +7,10 @@ every edge independently, the grid point that maximises the expected complete-da
 round lowers a family's likelihood.  `BranchLengthFitter` is the handle, `ml_branch_lengths` the stage on tree / MSA / site-rate
 directories, `nj_ml_trees` the tree estimator `nj_trees` + `ml_branch_lengths`.
 
-Out of scope: topology moves, a continuous (off-grid) optimiser, S > 32."""
+The handle also scores the nearest-neighbour interchanges of its trees from the messages its passes leave resident (`nni_moves`,
+`nni_scan`; the search on top of them is `_nni.py`).
+
+Out of scope: changing a handle's topology in place, a continuous (off-grid) optimiser, S > 32."""
 import ctypes
 import os
 import time
@@ -64,6 +67,8 @@ class BranchLengthFitter:
                       ((parent, np.int32), (length, np.float64), (rates, np.float64), (codes, np.int8))]
         self.device = _device_index() if device is None else int(device)
         self.last_kernel_ms = (0.0, 0.0)   # (passes, M-step) of the last round
+        self._parent = [np.asarray(p, dtype=np.int32) for p in parent]
+        self.last_nni_kernel_ms = (0.0, 0.0)   # (passes, scan) of the last nni_scan
         self._create()
 
     def _create(self) -> None:
@@ -112,6 +117,40 @@ class BranchLengthFitter:
         """(per family the log-likelihood of every site, their sums per family) at the current lengths"""
         _, ll, fam = self._get(True)
         return np.split(ll, np.cumsum(self.n_units)[:-1]), fam
+
+    def nni_moves(self) -> List[np.ndarray]:
+        """per family the int32 [n, 3] array of ALL nearest-neighbour interchanges (v, c, s) of its tree, node indices in
+        `tree.nodes()` order: v (internal, not the root) ascending, then c over the children of v, then s over the other children
+        of parent[v], children in node order (`_nni.enumerate_nni_moves`)"""
+        from ._nni import enumerate_nni_moves
+        return [enumerate_nni_moves(p) for p in self._parent]
+
+    def nni_scan(self, moves: Optional[Sequence] = None, per_site: bool = False):
+        """Score moves by likelihood at the current indices (`cb_bl_nni_scan`: one launch per family from the resident messages)
+        -> (moves, delta) and with `per_site` also ll_moves: per family the [n, 3] moves (`nni_moves()` when None; a family with
+        none is skipped), delta [n] = the log-likelihood of the rearranged tree minus the present one, and ll_moves [n, n_sites]
+        the rearranged tree's log-likelihood per site.  Changes nothing `round()`, `indices()` or `log_likelihoods()` return.
+        Sets `last_nni_kernel_ms` = (passes, scan)."""
+        moves = self.nni_moves() if moves is None else [np.ascontiguousarray(m, dtype=np.int32).reshape(-1, 3) for m in moves]
+        if len(moves) != self.n_nodes.size:
+            raise ValueError(f"nni_scan: {len(moves)} move lists for {self.n_nodes.size} families")
+        n_moves = np.array([len(m) for m in moves], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(moves).reshape(-1), dtype=np.int32)
+        delta = np.empty(int(n_moves.sum()))
+        sizes = n_moves.astype(np.int64) * self.n_units
+        ll = np.empty(int(sizes.sum())) if per_site else None
+        ms = (ctypes.c_double * 2)(0.0, 0.0)
+        rc = _lib.load().cb_bl_nni_scan(self._handle(), n_moves.ctypes.data, flat.ctypes.data, delta.ctypes.data,
+                                        ll.ctypes.data if per_site else None, None, ctypes.addressof(ms))
+        if rc == _lib.CB_EINVAL:   # a refused move list: the library's message names family, move and value
+            raise _lib.CherryBankError(f"cb_bl_nni_scan failed ({rc}): {_lib.load().cb_last_error().decode('utf-8', 'replace')}")
+        _lib.check(rc, "cb_bl_nni_scan")
+        self.last_nni_kernel_ms = (ms[0], ms[1])
+        deltas = np.split(delta, np.cumsum(n_moves)[:-1])
+        if not per_site:
+            return moves, deltas
+        lls = [x.reshape(int(k), int(u)) for x, k, u in zip(np.split(ll, np.cumsum(sizes)[:-1]), n_moves, self.n_units)]
+        return moves, deltas, lls
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None:

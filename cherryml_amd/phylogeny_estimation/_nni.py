@@ -1,0 +1,267 @@
+"""Topology search by nearest-neighbour interchange (NNI) on the branch-length handle (csrc/nni.hip.h, `cb_bl_nni_scan`;
+DESIGN.md section 18).
+
+A move on a rooted, possibly multifurcating tree is a triple of node indices (v, c, s) in `tree.nodes()` order: v internal and
+not the root, p = parent[v], c a child of v, s a child of p other than v.  It exchanges the subtrees of c and s; every node
+keeps the edge above it and that edge's length.  `BranchLengthFitter.nni_scan` scores all moves of a tree from the messages its
+passes leave resident; `select_nni` picks a set of moves at disjoint places, `apply_nni` makes the rearranged tree, and
+`ml_nni_trees` alternates the branch-length EM with scan / select / apply, keeping a candidate tree only if its likelihood at
+the same lengths is strictly higher.  `nj_nni_trees` is the tree estimator `nj_trees` + `ml_nni_trees`.
+
+Out of scope: SPR / TBR moves, changing a handle's topology in place (a rearranged tree gets a new handle), refitting site
+rates inside the search, S > 32."""
+import os
+import time
+from typing import Dict, List, Optional
+
+import numpy as np
+
+from .. import _lib
+from ..caching import cached_computation
+from ..io._tree import Tree, read_tree, write_tree
+from ._fast_cherries import quantization_points_ble
+from ._ml_lengths import DEFAULT_MAX_BANK_BYTES, BranchLengthFitter, _batches
+
+
+def enumerate_nni_moves(parent) -> np.ndarray:
+    """int32 [n, 3]: all moves (v, c, s) of the tree with this parent array (the root: -1) -- v ascending, then c over the
+    children of v, then s over the children of parent[v] other than v, children in node order"""
+    parent = np.asarray(parent)
+    ch: List[List[int]] = [[] for _ in parent]
+    for v, p in enumerate(parent):
+        if p >= 0:
+            ch[int(p)].append(v)
+    out = [(v, c, s) for v, p in enumerate(parent) if p >= 0 and ch[v] for c in ch[v] for s in ch[int(p)] if s != v]
+    return np.array(out, dtype=np.int32).reshape(-1, 3)
+
+
+def _parent_array(tree: Tree) -> np.ndarray:
+    index = {v: i for i, v in enumerate(tree.nodes())}
+    parent = np.full(len(index), -1, dtype=np.int32)
+    for u, v, _ in tree.edges():
+        parent[index[v]] = index[u]
+    return parent
+
+
+def apply_nni(tree: Tree, moves) -> Tree:
+    """A new `Tree` with the nodes of `tree` in the same order and, for every move (v, c, s) (node indices in `tree.nodes()`
+    order), the subtrees of c and s exchanged: parent[c] = parent[v], parent[s] = v.  Every node keeps the length of the edge
+    above it, and the edges keep their order.  ValueError for a triple that is no move of the tree and for a set of moves that
+    share a node (of the four of a move: parent[v], v, c, s): such moves do not commute."""
+    moves = np.asarray(moves, dtype=np.int64).reshape(-1, 3)
+    nodes = tree.nodes()
+    parent = _parent_array(tree)
+    n = len(nodes)
+    new = parent.copy()
+    used: Dict[int, int] = {}
+    for k, (v, c, s) in enumerate(moves.tolist()):
+        if not (0 <= v < n and 0 <= c < n and 0 <= s < n):
+            raise ValueError(f"apply_nni: move {k} = ({v}, {c}, {s}): an index outside [0, {n})")
+        p = int(parent[v])
+        if p < 0 or parent[c] != v or s == v or parent[s] != p:
+            raise ValueError(f"apply_nni: move {k} = ({v}, {c}, {s}) is no move of the tree (v internal and not the root, c a "
+                             f"child of v, s another child of parent[v] = {p})")
+        for w in (p, v, c, s):
+            if w in used:
+                raise ValueError(f"apply_nni: moves {used[w]} and {k} share node {w} ({nodes[w]})")
+        for w in (p, v, c, s):
+            used[w] = k
+        new[c], new[s] = p, v
+    index = {v: i for i, v in enumerate(nodes)}
+    out = Tree()
+    out.add_nodes(nodes)
+    out.add_edges([(nodes[int(new[index[v]])], v, t) for _, v, t in tree.edges()])
+    return out
+
+
+def select_nni(moves, delta, parent, min_gain: float = 0.0) -> np.ndarray:
+    """The indices (into `moves`) of a set of moves at disjoint places, greedily by descending `delta` (ties: the lower move
+    index): only moves with delta > min_gain are considered, and a move is taken only if none of its four nodes {parent[v], v,
+    c, s} belongs to a move already taken.  In the order taken."""
+    moves = np.asarray(moves, dtype=np.int64).reshape(-1, 3)
+    delta = np.asarray(delta, dtype=np.float64).reshape(-1)
+    parent = np.asarray(parent)
+    if delta.size != len(moves):
+        raise ValueError(f"select_nni: {len(moves)} moves and {delta.size} deltas")
+    order = [int(m) for m in np.argsort(-delta, kind="stable") if delta[m] > min_gain]
+    used, taken = set(), []
+    for m in order:
+        v, c, s = (int(x) for x in moves[m])
+        four = {int(parent[v]), v, c, s}
+        if used & four:
+            continue
+        used |= four
+        taken.append(m)
+    return np.array(taken, dtype=np.int64)
+
+
+@cached_computation(output_dirs=["output_tree_dir", "output_likelihood_dir"], exclude_args=["max_bank_bytes"])
+def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: List[str], rate_matrix_path: str,
+                 num_nni_rounds: int = 10, num_rounds: int = 10, quantization_grid_center: float = 0.03,
+                 quantization_grid_step: float = 1.1, quantization_grid_num_steps: int = 64, output_tree_dir: Optional[str] = None,
+                 output_likelihood_dir: Optional[str] = None, max_bank_bytes: int = DEFAULT_MAX_BANK_BYTES, _version="1") -> None:
+    """Improve the topologies of `<tree_dir>/<family>.txt` by likelihood: at most `num_nni_rounds` times, per family, fit the
+    lengths of the current tree (`BranchLengthFitter`, at most `num_rounds` EM rounds), score ALL its nearest-neighbour
+    interchanges (`nni_scan`), select those of positive gain at disjoint places (`select_nni`) and apply them (`apply_nni`).
+    The gains of simultaneous moves are not additive, so the candidate tree is kept only if its log-likelihood at the same
+    lengths -- `log_likelihoods()` of the next round's fitter on it, before any EM round -- is strictly above the one before
+    the moves (so a round costs one handle); otherwise the family retries with the first half of its selected moves, down to
+    one move (whose gain is exact).  A family with no accepted move is finished; a family that still moved in the last NNI
+    round gets EM rounds on its final topology.
+    Per family: `<output_tree_dir>/<family>.txt` (the input's node names and their order, every length a grid point),
+    `<family>.nni` (per NNI round `<round> <log-likelihood before> <moves scanned> <selected> <applied> <log-likelihood after,
+    same lengths>`, then `final <log-likelihood of the written tree>`: no number is below the one before it),
+    `<family>.profiling`, and `<output_likelihood_dir>/<family>.txt` as `ml_branch_lengths` writes it."""
+    from ..counting._host import read_msa, read_site_rates
+    from ..counting._stage import _device_index
+    from ..evaluation._likelihood import (_family_units, _stationary_distribution, dp_likelihood_computation_batch,
+                                          write_log_likelihood)
+    from ..io import read_rate_matrix
+    if output_tree_dir is None or output_likelihood_dir is None:
+        raise ValueError("output_tree_dir and output_likelihood_dir are required")
+    if _lib.load().cb_device_count() <= 0:
+        raise _lib.CherryBankError("ml_nni_trees: no HIP device visible; the search runs on the MI355X only (no CPU fallback)")
+    st_all = time.time()
+    for d in (output_tree_dir, output_likelihood_dir):
+        os.makedirs(d, exist_ok=True)
+    rm = read_rate_matrix(rate_matrix_path)
+    alphabet = [str(c) for c in rm.columns]
+    Q = np.ascontiguousarray(rm.to_numpy(), dtype=np.float64)
+    pi_root = _stationary_distribution(Q)
+    grid = np.array(quantization_points_ble(quantization_grid_center, quantization_grid_step, quantization_grid_num_steps))
+    device = _device_index()
+    trees, msas, rates, codes = [], [], [], []
+    for family in families:
+        tree = read_tree(os.path.join(tree_dir, family + ".txt"))
+        msa = read_msa(os.path.join(msa_dir, family + ".txt"))
+        r = np.asarray(read_site_rates(os.path.join(site_rates_dir, family + ".txt")), dtype=np.float64)
+        trees.append(tree), msas.append(msa), rates.append(r)
+        # (the codes' rows follow tree.nodes(), which no move changes)
+        codes.append(_family_units(tree, msa, None, len(r), alphabet, False)[2])
+    F = len(families)
+    logs: List[List[str]] = [[] for _ in families]
+    prof = [dict(create_time=0.0, scan_time=0.0, scan_kernel_ms=0.0, fit_time=0.0, handles=0, nni_rounds=0, moves_applied=0)
+            for _ in families]
+    final_ll: List[Optional[float]] = [None] * F
+    bank_bytes = [2 * grid.size * np.unique(r).size * Q.size * 8 for r in rates]
+    # Per family: rnd = its NNI round; trees[f] = the tree the next handle takes -- the input, or a candidate (fitted[f] with the
+    # moves sel[f] applied) that has to beat before[f].  ONE handle per pass over the work list: on a candidate its
+    # log_likelihoods() before any EM round decides (the lengths are the fitted ones: grid points snap to themselves), and the
+    # accepted families go on in the same handle with the EM rounds and the scan of their next round.
+    rnd = [0] * F
+    before: List[Optional[float]] = [None] * F
+    fitted: List[Optional[Tree]] = [None] * F
+    sel: List[Optional[np.ndarray]] = [None] * F
+    scanned, selected = [0] * F, [0] * F
+    work = list(range(F))
+    while work:
+        nxt: List[int] = []
+        for batch in _batches([bank_bytes[f] for f in work], int(max_bank_bytes)):
+            fams = [work[k] for k in batch]
+            st = time.time()
+            with BranchLengthFitter([trees[f] for f in fams], [codes[f] for f in fams], [rates[f] for f in fams], grid, Q, pi_root,
+                                    device=device) as fit:
+                t_create = time.time() - st
+                go = np.ones(len(fams), dtype=bool)            # the input tree, or an accepted candidate
+                if any(before[f] is not None for f in fams):
+                    _, ll0 = fit.log_likelihoods()
+                    for k, f in enumerate(fams):
+                        if before[f] is None:
+                            continue
+                        if ll0[k] > before[f]:
+                            logs[f].append(f"{rnd[f]} {before[f]!r} {scanned[f]} {selected[f]} {len(sel[f])} {float(ll0[k])!r}\n")
+                            prof[f]["moves_applied"] += len(sel[f])
+                            rnd[f] += 1
+                        else:
+                            go[k] = False
+                live = go.copy()                               # (a refused candidate's rounds are nobody's)
+                for _ in range(int(num_rounds)):
+                    if not live.any():
+                        break
+                    n_changed, _ = fit.round()
+                    live &= n_changed > 0
+                lengths = fit.lengths()
+                _, fam_ll = fit.log_likelihoods()
+                want = [bool(go[k]) and rnd[f] < int(num_nni_rounds) for k, f in enumerate(fams)]
+                st_scan = time.time()
+                if any(want):
+                    moves, delta = fit.nni_scan([m if w else m[:0] for m, w in zip(fit.nni_moves(), want)])
+                t_scan, ms_scan = time.time() - st_scan, fit.last_nni_kernel_ms[1]
+            for k, f in enumerate(fams):
+                for key, x in (("create_time", t_create), ("scan_time", t_scan), ("scan_kernel_ms", ms_scan),
+                               ("fit_time", time.time() - st)):
+                    prof[f][key] += x / len(fams)              # (shares of the batch)
+                prof[f]["handles"] += 1
+                if not go[k]:                                  # refused: half of the moves, down to one, whose gain is exact
+                    if len(sel[f]) > 1:
+                        sel[f] = sel[f][:len(sel[f]) // 2]
+                        trees[f] = apply_nni(fitted[f], sel[f])
+                        nxt.append(f)
+                    else:                                      # (rounding only)
+                        logs[f].append(f"{rnd[f]} {before[f]!r} {scanned[f]} {selected[f]} 0 {before[f]!r}\n")
+                        trees[f], final_ll[f] = fitted[f], before[f]
+                    continue
+                t = Tree()
+                t.add_nodes(trees[f].nodes())
+                t.add_edges([(u, v, lengths[k][v]) for u, v, _ in trees[f].edges()])
+                trees[f], ll = t, float(fam_ll[k])
+                if not want[k]:                                # the topology of the last round's moves after its own EM rounds
+                    final_ll[f] = ll
+                    continue
+                prof[f]["nni_rounds"] += 1
+                s = moves[k][select_nni(moves[k], delta[k], _parent_array(t))]
+                scanned[f], selected[f] = len(moves[k]), len(s)
+                if len(s) == 0:                                # no move gains: finished
+                    logs[f].append(f"{rnd[f]} {ll!r} {scanned[f]} 0 0 {ll!r}\n")
+                    final_ll[f] = ll
+                    continue
+                fitted[f], before[f], sel[f] = t, ll, s
+                trees[f] = apply_nni(t, s)
+                nxt.append(f)
+        work = nxt
+    st = time.time()
+    lls = dp_likelihood_computation_batch(trees, msas, [None] * F, [[float(x) for x in r] for r in rates], alphabet, pi_root, Q,
+                                          device=device)
+    t_ll = (time.time() - st) / max(F, 1)
+    t_total = (time.time() - st_all) / max(F, 1)
+    for f, family in enumerate(families):
+        write_tree(trees[f], os.path.join(output_tree_dir, family + ".txt"))
+        with open(os.path.join(output_tree_dir, family + ".nni"), "w") as fh:
+            fh.write("".join(logs[f]) + f"final {final_ll[f]!r}\n")
+        write_log_likelihood(lls[f], os.path.join(output_likelihood_dir, family + ".txt"))
+        with open(os.path.join(output_tree_dir, family + ".profiling"), "w") as fh:
+            fh.write("".join(f"{k}: {v}\n" for k, v in prof[f].items()) + f"likelihood_time: {t_ll}\ntotal_time: {t_total}")
+
+
+def nj_nni_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, num_rate_categories: int, max_iters: int = 50,
+                 num_processes: int = 1, num_rounds: int = 10, num_nni_rounds: int = 10, output_tree_dir: Optional[str] = None,
+                 output_site_rates_dir: Optional[str] = None, output_likelihood_dir: Optional[str] = None, remake=False,
+                 quantization_grid_center=0.03, quantization_grid_step=1.1, quantization_grid_num_steps=64, verbose=True,
+                 seed=1234) -> Dict[str, str]:
+    """`nj_trees`, then `ml_nni_trees` on its trees at its site rates and the same grid: `nj_ml_trees`' interface plus
+    `num_nni_rounds`, and under `functools.partial` a `tree_estimator` of the end-to-end pipelines.  Returns the output
+    directories: `output_tree_dir` / `output_likelihood_dir` hold the searched trees and their likelihoods,
+    `output_site_rates_dir` is `nj_trees`' own.  Both stages are cached on their own.  With no cache directory the three output
+    directories are required and the neighbour-joining trees and likelihoods go to their `nj_trees` subdirectories."""
+    from ..caching import get_cache_dir
+    from ._nj import nj_trees
+    if _lib.load().cb_device_count() <= 0:
+        raise _lib.CherryBankError("nj_nni_trees: no HIP device visible; the search runs on the MI355X only (no CPU fallback)")
+    nj_out = dict(output_tree_dir=None, output_site_rates_dir=output_site_rates_dir, output_likelihood_dir=None)
+    if get_cache_dir() is None:
+        if output_tree_dir is None or output_site_rates_dir is None or output_likelihood_dir is None:
+            raise ValueError("output_tree_dir, output_site_rates_dir and output_likelihood_dir are required without a cache directory")
+        nj_out.update(output_tree_dir=os.path.join(output_tree_dir, "nj_trees"),
+                      output_likelihood_dir=os.path.join(output_likelihood_dir, "nj_trees"))
+    grid_args = dict(quantization_grid_center=quantization_grid_center, quantization_grid_step=quantization_grid_step,
+                     quantization_grid_num_steps=quantization_grid_num_steps)
+    nj = nj_trees(msa_dir=msa_dir, families=families, rate_matrix_path=rate_matrix_path, num_rate_categories=num_rate_categories,
+                  max_iters=max_iters, num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, **grid_args, **nj_out)
+    nj = nj if nj is not None else nj_out
+    out = dict(output_tree_dir=output_tree_dir, output_likelihood_dir=output_likelihood_dir)
+    ml = ml_nni_trees(tree_dir=nj["output_tree_dir"], msa_dir=msa_dir, site_rates_dir=nj["output_site_rates_dir"],
+                      families=families, rate_matrix_path=rate_matrix_path, num_nni_rounds=num_nni_rounds, num_rounds=num_rounds,
+                      **grid_args, **out)
+    ml = ml if ml is not None else out
+    return dict(output_tree_dir=ml["output_tree_dir"], output_site_rates_dir=nj["output_site_rates_dir"],
+                output_likelihood_dir=ml["output_likelihood_dir"])

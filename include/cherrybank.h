@@ -585,7 +585,24 @@ int cb_em_destroy(cb_em h);
  * cb_bl_get: index [sum n_nodes] the current indices (the root's: -1), ll [sum n_units] (may be NULL) the log-likelihood of every
  *   site and fam_ll [n_fam] (may be NULL) their sums per family, both at the CURRENT lengths.
  * No atomics, fixed orders: two handles on the same input give the same indices and bitwise-equal likelihoods.  One call at a
- * time per handle. */
+ * time per handle.
+ *
+ * cb_bl_nni_scan: the nearest-neighbour interchanges of the handle's trees, scored by likelihood at the CURRENT indices.  A move
+ *   of family f is a triple (v, c, s) of node indices within the family: v internal and not the root, c a child of v, s a child
+ *   of p = parent[v] other than v.  It exchanges the subtrees of c and s (parent[c] = p, parent[s] = v); every node keeps the
+ *   edge above it and its grid index.  n_moves [n_fam] (0: the family is skipped, no pass runs for it), moves
+ *   [sum n_moves][3] the families' triples concatenated.  Every triple is validated on the host before any device work
+ *   (CB_EINVAL names family, move and value: an index out of range, v the root or a leaf, c no child of v, s == v, s no child of
+ *   parent[v], a negative count).  The call runs the inside and outside passes of the scanned families at the current indices
+ *   (after cb_bl_round the resident messages belong to the round's start), then one launch per family (per chunk of its moves,
+ *   under a fixed byte bound on ll') forms for every move and site the exact log-likelihood of the rearranged tree from the
+ *   messages at v and p alone.  Out: delta [sum n_moves] = sum over the sites of (ll' - l_u), in a fixed order (a site whose
+ *   l_u is -inf contributes 0); ll_moves (may be NULL) per family [n_moves[f]][n_units[f]] in the caller's unit order; fam_ll
+ *   (may be NULL) [n_fam] the log-likelihood at the current indices -- cb_bl_get's, bit for bit; NaN for a skipped family whose
+ *   likelihood the handle does not hold; kernel_ms (may be NULL) [2]: the device time of the passes and of the scan.
+ *   The scan changes nothing cb_bl_round or cb_bl_get return: not the indices, not the fixed points, not one bit of a
+ *   likelihood.  ll' lives in a buffer of the call, freed before it returns; a move's results do not depend on the other moves
+ *   or families of the call.  The topology of a handle is fixed: a rearranged tree gets a new handle. */
 #define CB_BL_MAX_CATS 64
 typedef struct cb_bl_s *cb_bl;
 int cb_bl_create(int device, int S, int T, const double *grid, const double *Q, const double *pi_root, int n_fam,
@@ -593,6 +610,8 @@ int cb_bl_create(int device, int S, int T, const double *grid, const double *Q, 
                  const int8_t *codes, cb_bl *out);
 int cb_bl_round(cb_bl h, int *n_changed, double *fam_ll, double *kernel_ms);
 int cb_bl_get(cb_bl h, int *index, double *ll, double *fam_ll);
+int cb_bl_nni_scan(cb_bl h, const int *n_moves, const int *moves, double *delta, double *ll_moves, double *fam_ll,
+                   double *kernel_ms);
 int cb_bl_destroy(cb_bl h);
 
 /* ---- the maximum-likelihood rate category of every site on fixed full trees (S <= 32) ----------------------------------------
