@@ -1,9 +1,11 @@
 // libcherrybank: maximum-likelihood branch lengths on fixed trees by EM, on a resident handle (bl.hip.h; include/cherrybank.h,
-// cb_bl_*), and the nearest-neighbour-interchange scan on the handle's resident messages (nni.hip.h; cb_bl_nni_scan).
+// cb_bl_*), the nearest-neighbour-interchange scan on the handle's resident messages (nni.hip.h; cb_bl_nni_scan) and the marginal
+// ancestral reconstruction from the same messages (anc.hip.h; cb_bl_ancestral).
 #include "cb_internal.hip.h"
 #include "common.hip.h"
 #include "bl.hip.h"
 #include "nni.hip.h"
+#include "anc.hip.h"
 #include "em_host.hip.h"
 
 struct cb_bl_s {
@@ -450,5 +452,101 @@ extern "C" int cb_bl_nni_scan(cb_bl_s *h, const int *n_moves, const int *moves, 
   }
   if (fam_ll)
     for (int f = 0; f < n_fam; ++f) fam_ll[f] = h->ll_fresh[f] ? h->fam_ll[f] : std::nan("");
+  return CB_OK;
+}
+
+namespace {
+constexpr size_t ANC_POST_BYTES = (size_t)256 << 20;   // post[node][unit][S] of one chunk of nodes, at most (one node always goes)
+
+// the bound above, or the test hook CB_ANC_POST_BYTES (cb_internal.hip.h): the results do not depend on the chunking
+size_t anc_post_bound() {
+  const char *s = cb_test_hook("CB_ANC_POST_BYTES");
+  const long long x = s ? atoll(s) : 0;
+  return x > 0 ? (size_t)x : ANC_POST_BYTES;
+}
+}  // namespace
+
+extern "C" int cb_bl_ancestral(cb_bl_s *h, int8_t *state, double *conf, double *post, double *fam_ll, double *kernel_ms) {
+  static const char *who = "cb_bl_ancestral";
+  if (!h) return fail(CB_EINVAL, "%s: NULL handle", who);
+  if (!state) return fail(CB_EINVAL, "%s: NULL argument (state)", who);
+  const int n_fam = h->n_fam, S = h->S, upw = 64 / S;
+  // nodes per launch: all of a family's, fewer under the bound on post and where nodes x site tiles would pass 2^31
+  std::vector<int> chunk(n_fam, 0);
+  size_t max_out = 0;
+  const size_t bound = anc_post_bound();
+  for (int f = 0; f < n_fam; ++f) {
+    const EmFamHost &F = h->fam[f];
+    const size_t n_blocks = ((size_t)F.n_units + upw - 1) / upw;
+    size_t fit = (size_t)INT32_MAX / n_blocks;
+    if (post) fit = std::min(fit, bound / ((size_t)F.n_units * S * sizeof(double)));
+    chunk[f] = (int)std::min<size_t>(F.n_nodes, std::max<size_t>(fit, 1));
+    if ((size_t)chunk[f] * n_blocks > (size_t)INT32_MAX)
+      return fail(CB_EINVAL, "%s: family %d: %zu site tiles (at most 2^31 - 1 per launch)", who, f, n_blocks);
+    max_out = std::max(max_out, (size_t)chunk[f] * F.n_units);
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.0;
+  // the messages at the current indices: after a round the resident ones are its start's
+  if (kernel_ms) HIP_TRY(hipEventRecord(h->ev[0], 0));
+  for (int f = 0; f < n_fam; ++f) bl_launch_passes(h, f, true);
+  HIP_TRY(hipGetLastError());
+  if (kernel_ms) {
+    float ms = 0.f;
+    HIP_TRY(hipEventRecord(h->ev[1], 0));
+    HIP_TRY(hipEventSynchronize(h->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    kernel_ms[0] = ms;
+  }
+  int rc = CB_OK;
+  std::vector<int8_t> host_state(max_out);
+  std::vector<double> host_conf(conf ? max_out : 0), host_post(post ? max_out * S : 0);
+  CbDevBufs bufs;   // this call's: freed on every return path
+  signed char *dstate = bufs.up<signed char>(nullptr, max_out, rc);
+  double *dconf = bufs.up<double>(nullptr, max_out, rc), *dpost = post ? bufs.up<double>(nullptr, max_out * S, rc) : nullptr;
+  if (rc != CB_OK) return rc;
+  for (int f = 0; f < n_fam; ++f) {
+    const EmFamHost &F = h->fam[f];
+    const size_t nb = h->off_c[f];
+    const int U = F.n_units;
+    AncArgs a{};
+    a.S = S; a.n_units = U; a.n_cats = F.n_cats; a.root = F.root; a.n_blocks = (U + upw - 1) / upw;
+    a.parent = h->dparent + h->off_n[f]; a.child_ptr = h->dcp + h->off_n[f] + f; a.child_idx = h->dci + h->off_n[f];
+    a.qb = h->dqb + h->off_q[f]; a.unit_cat = h->duc + h->off_u[f]; a.codes = h->dcodes + nb; a.P = h->dP; a.pi_root = h->dpi;
+    a.msg = h->dmsg + nb * S; a.U = h->dU + nb * S; a.state = dstate; a.conf = dconf; a.post = dpost;
+    for (int v0 = 0; v0 < F.n_nodes; v0 += chunk[f]) {
+      const int nv = std::min(chunk[f], F.n_nodes - v0);
+      a.node0 = v0;
+      if (kernel_ms) HIP_TRY(hipEventRecord(h->ev[1], 0));
+      hipLaunchKernelGGL(anc_post_kernel, dim3((unsigned)nv * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
+      HIP_TRY(hipGetLastError());
+      if (kernel_ms) {
+        float ms = 0.f;
+        HIP_TRY(hipEventRecord(h->ev[2], 0));
+        HIP_TRY(hipEventSynchronize(h->ev[2]));
+        HIP_TRY(hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
+        kernel_ms[1] += ms;
+      }
+      // device (category) order -> the caller's unit order (the next chunk writes the same buffers: these copies wait for this one)
+      const size_t cnt = (size_t)nv * U, base = nb + (size_t)v0 * U;
+      HIP_TRY(hipMemcpy(host_state.data(), dstate, cnt * sizeof(int8_t), hipMemcpyDeviceToHost));
+      if (conf) HIP_TRY(hipMemcpy(host_conf.data(), dconf, cnt * sizeof(double), hipMemcpyDeviceToHost));
+      if (post) HIP_TRY(hipMemcpy(host_post.data(), dpost, cnt * S * sizeof(double), hipMemcpyDeviceToHost));
+      for (int v = 0; v < nv; ++v)
+        for (int k = 0; k < U; ++k) {
+          const size_t src = (size_t)v * U + k, dst = base + (size_t)v * U + F.perm[k];
+          state[dst] = host_state[src];
+          if (conf) conf[dst] = host_conf[src];
+          if (post) std::copy(host_post.begin() + src * S, host_post.begin() + (src + 1) * S, post + dst * S);
+        }
+    }
+  }
+  // dll now holds l_u at the current indices -- the bits cb_bl_get's inside pass would write
+  std::vector<char> stale(n_fam);
+  for (int f = 0; f < n_fam; ++f) stale[f] = !h->ll_fresh[f];
+  rc = bl_read_ll(h, stale, nullptr);
+  if (rc != CB_OK) return rc;
+  std::fill(h->ll_fresh.begin(), h->ll_fresh.end(), 1);
+  if (fam_ll) std::copy(h->fam_ll.begin(), h->fam_ll.end(), fam_ll);
   return CB_OK;
 }

@@ -96,7 +96,8 @@ int cb_tb_launch_ew(const CbTbEwArgs &a, hipStream_t stream, hipEvent_t stop, in
 //   time basis maintenance (cherrybank.hip): CB_TB_TEST_GROWTH, CB_TB_TEST_WARN;
 //   eigensolver (train_host.hip.h, eigh_large_host.hip.h): CB_EIGH_HOST, CB_NO_HYBRID, CB_EIGH_SHORT_PLAN;
 //   counts (create_host.hip.h): CB_NO_SYM;   faults (cherrybank.hip, train_host.hip.h): CB_FAULT_INJECT;
-//   the site-rate scan's candidate chunks (cb_sr.hip): CB_SR_MSG_BYTES;   the NNI scan's move chunks (cb_bl.hip): CB_NNI_LL_BYTES.
+//   the site-rate scan's candidate chunks (cb_sr.hip): CB_SR_MSG_BYTES;   the NNI scan's move chunks (cb_bl.hip): CB_NNI_LL_BYTES;
+//   the ancestral reconstruction's node chunks (cb_bl.hip): CB_ANC_POST_BYTES.
 // (CB_DEBUG and CB_TRACE_SLOW only log; CB_BANK_STREAMS is a documented opt-in.)
 static inline const char *cb_test_hook(const char *name) {
   const char *on = getenv("CB_TEST_HOOKS");

@@ -8,7 +8,8 @@ round lowers a family's likelihood.  `BranchLengthFitter` is the handle, `ml_bra
 directories, `nj_ml_trees` the tree estimator `nj_trees` + `ml_branch_lengths`.
 
 The handle also scores the nearest-neighbour interchanges of its trees from the messages its passes leave resident (`nni_moves`,
-`nni_scan`; the search on top of them is `_nni.py`).
+`nni_scan`; the search on top of them is `_nni.py`) and reconstructs the marginal posterior of the state at
+every node from the same messages (`ancestral_states`; the stage is `_ancestral.py`).
 
 Out of scope: changing a handle's topology in place, a continuous (off-grid) optimiser, S > 32."""
 import ctypes
@@ -69,6 +70,7 @@ class BranchLengthFitter:
         self.last_kernel_ms = (0.0, 0.0)   # (passes, M-step) of the last round
         self._parent = [np.asarray(p, dtype=np.int32) for p in parent]
         self.last_nni_kernel_ms = (0.0, 0.0)   # (passes, scan) of the last nni_scan
+        self.last_ancestral_kernel_ms = (0.0, 0.0)   # (passes, reconstruction) of the last ancestral_states
         self._create()
 
     def _create(self) -> None:
@@ -151,6 +153,32 @@ class BranchLengthFitter:
             return moves, deltas
         lls = [x.reshape(int(k), int(u)) for x, k, u in zip(np.split(ll, np.cumsum(sizes)[:-1]), n_moves, self.n_units)]
         return moves, deltas, lls
+
+    def ancestral_states(self, posteriors: bool = False):
+        """The marginal posterior of the state at EVERY node (root, internal nodes, leaves) at the current indices
+        (`cb_bl_ancestral`: one launch per family from the resident messages) -> (states, confidence) and with `posteriors` also
+        the whole distributions: per family int8 [n_nodes, n_sites] the most probable state (the lowest index among exactly equal
+        maxima), float64 [n_nodes, n_sites] its posterior and float64 [n_nodes, n_sites, S]; rows in `tree.nodes()` order.  An
+        observed leaf character gets its own state with posterior 1, a gapped one is imputed; a site that is impossible under the
+        model gets state -1, confidence 0 and a zero posterior.  Changes nothing `round()`, `indices()`, `log_likelihoods()` or
+        `nni_scan()` return.  Sets `last_ancestral_kernel_ms` = (passes, reconstruction)."""
+        sizes = self.n_nodes.astype(np.int64) * self.n_units
+        total = int(sizes.sum())
+        state = np.empty(total, dtype=np.int8)
+        conf = np.empty(total)
+        post = np.empty(total * self.S) if posteriors else None
+        ms = (ctypes.c_double * 2)(0.0, 0.0)
+        rc = _lib.load().cb_bl_ancestral(self._handle(), state.ctypes.data, conf.ctypes.data, post.ctypes.data if posteriors else None,
+                                         None, ctypes.addressof(ms))
+        _lib.check(rc, "cb_bl_ancestral")
+        self.last_ancestral_kernel_ms = (ms[0], ms[1])
+        cuts = np.cumsum(sizes)[:-1]
+        shapes = list(zip(self.n_nodes.tolist(), self.n_units.tolist()))
+        states = [x.reshape(sh) for x, sh in zip(np.split(state, cuts), shapes)]
+        confs = [x.reshape(sh) for x, sh in zip(np.split(conf, cuts), shapes)]
+        if not posteriors:
+            return states, confs
+        return states, confs, [x.reshape(sh + (self.S,)) for x, sh in zip(np.split(post, cuts * self.S), shapes)]
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None:

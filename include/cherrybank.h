@@ -602,7 +602,23 @@ int cb_em_destroy(cb_em h);
  *   likelihood the handle does not hold; kernel_ms (may be NULL) [2]: the device time of the passes and of the scan.
  *   The scan changes nothing cb_bl_round or cb_bl_get return: not the indices, not the fixed points, not one bit of a
  *   likelihood.  ll' lives in a buffer of the call, freed before it returns; a move's results do not depend on the other moves
- *   or families of the call.  The topology of a handle is fixed: a rearranged tree gets a new handle. */
+ *   or families of the call.  The topology of a handle is fixed: a rearranged tree gets a new handle.
+ *
+ * cb_bl_ancestral: the marginal posterior of the state at EVERY node of the handle's trees -- root, internal nodes and leaves --
+ *   at the CURRENT indices.  The call runs the inside and outside passes of every family at the current indices (as
+ *   cb_bl_nni_scan does, and for its reason), then one launch per family (per chunk of its nodes) forms for every (node, site)
+ *   z = L_w + U_w in log space -- L_w the inside part (the children's messages; at a leaf 0 where the code is a gap or the
+ *   state, else -inf), U_w the outside part (log pi_root at the root, the resident outside message at an internal node, and at a
+ *   leaf one S x S product through the edge above it) -- and post[a] = exp(z[a] - max z) / sum_b exp(z[b] - max z).  Out, per
+ *   family [n_nodes[f]][n_units[f]], the families concatenated, in the caller's unit order: state (required) the most probable
+ *   state (int8, the lowest index among exactly equal maxima), conf (may be NULL) its posterior, post (may be NULL)
+ *   [n_nodes[f]][n_units[f]][S] the whole posterior.  An observed leaf character gets its own state with posterior 1; a gapped
+ *   one is imputed.  A site that is impossible under the model (l_u = -inf) gets state -1, conf 0 and post 0, never NaN.
+ *   fam_ll (may be NULL) [n_fam] the log-likelihood at the current indices -- cb_bl_get's, bit for bit; kernel_ms (may be NULL)
+ *   [2]: the device time of the passes and of the reconstruction.  CB_EINVAL for a NULL handle or a NULL state.
+ *   The call changes nothing cb_bl_round, cb_bl_get or cb_bl_nni_scan return.  Its device buffers are its own, freed before it
+ *   returns; with post a family's nodes go in chunks that keep the device copy of post under 256 MiB (one node always goes);
+ *   a node's results do not depend on the chunking or on the other nodes or families of the call. */
 #define CB_BL_MAX_CATS 64
 typedef struct cb_bl_s *cb_bl;
 int cb_bl_create(int device, int S, int T, const double *grid, const double *Q, const double *pi_root, int n_fam,
@@ -612,6 +628,7 @@ int cb_bl_round(cb_bl h, int *n_changed, double *fam_ll, double *kernel_ms);
 int cb_bl_get(cb_bl h, int *index, double *ll, double *fam_ll);
 int cb_bl_nni_scan(cb_bl h, const int *n_moves, const int *moves, double *delta, double *ll_moves, double *fam_ll,
                    double *kernel_ms);
+int cb_bl_ancestral(cb_bl h, int8_t *state, double *conf, double *post, double *fam_ll, double *kernel_ms);
 int cb_bl_destroy(cb_bl h);
 
 /* ---- the maximum-likelihood rate category of every site on fixed full trees (S <= 32) ----------------------------------------
