@@ -129,6 +129,35 @@ def load():
     return lib
 
 
+class ResidentHandle:
+    """The lifecycle of a resident handle of the library, kept in `self._h`: a subclass names its destroy function in `_destroy`.
+    A context manager; `close()` frees the handle (once), `_handle()` refuses a closed one."""
+    _destroy = ""
+    _h = None
+
+    def _handle(self):
+        if self._h is None:
+            raise CherryBankError(f"{type(self).__name__} is closed")
+        return self._h
+
+    def close(self) -> None:
+        if self._h is not None:
+            getattr(load(), self._destroy)(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def check(rc: int, what: str):
     if rc == 0:
         return

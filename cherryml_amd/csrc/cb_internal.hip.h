@@ -1,6 +1,8 @@
 // Shared by the translation units of libcherrybank: error reporting and small host-side helpers.
 // (cherrybank.hip: handle, bank entry points, trainers; cb_bank_fused.hip: the one-launch bank kernel; cb_tbasis.hip: the bank in a
-// time basis; cb_counting.hip; cb_ble.hip; cb_likelihood.hip; cb_host_io.hip; cb_simulate.hip; cb_em.hip; cb_bl.hip; cb_sr.hip.)
+// time basis; cb_counting.hip; cb_ble.hip; cb_likelihood.hip; cb_host_io.hip; cb_simulate.hip; cb_em.hip; cb_bl.hip; cb_sr.hip.
+// The tree EM handles' own scaffold -- forest layout, resident buffers, the two passes, the way back of l_u -- is em_layout.h
+// (HIP-free) and em_host.hip.h; what they take from here is cb_test_hook / cb_hook_bytes, CbDevBufs and CbKernelTimer.)
 #pragma once
 #include "../../include/cherrybank.h"
 
@@ -96,12 +98,18 @@ int cb_tb_launch_ew(const CbTbEwArgs &a, hipStream_t stream, hipEvent_t stop, in
 //   time basis maintenance (cherrybank.hip): CB_TB_TEST_GROWTH, CB_TB_TEST_WARN;
 //   eigensolver (train_host.hip.h, eigh_large_host.hip.h): CB_EIGH_HOST, CB_NO_HYBRID, CB_EIGH_SHORT_PLAN;
 //   counts (create_host.hip.h): CB_NO_SYM;   faults (cherrybank.hip, train_host.hip.h): CB_FAULT_INJECT;
-//   the site-rate scan's candidate chunks (cb_sr.hip): CB_SR_MSG_BYTES;   the NNI scan's move chunks (cb_bl.hip): CB_NNI_LL_BYTES;
-//   the ancestral reconstruction's node chunks (cb_bl.hip): CB_ANC_POST_BYTES.
+//   chunk bounds (cb_hook_bytes below) -- the site-rate scan's candidates (cb_sr.hip): CB_SR_MSG_BYTES; the NNI scan's moves
+//     (cb_bl.hip): CB_NNI_LL_BYTES; the ancestral reconstruction's nodes (cb_bl.hip): CB_ANC_POST_BYTES.
 // (CB_DEBUG and CB_TRACE_SLOW only log; CB_BANK_STREAMS is a documented opt-in.)
 static inline const char *cb_test_hook(const char *name) {
   const char *on = getenv("CB_TEST_HOOKS");
   return (on && on[0] == '1') ? getenv(name) : nullptr;
+}
+// a chunk bound in bytes: `bytes`, or the positive number the test hook `name` holds
+static inline size_t cb_hook_bytes(const char *name, size_t bytes) {
+  const char *s = cb_test_hook(name);
+  const long long x = s ? atoll(s) : 0;
+  return x > 0 ? (size_t)x : bytes;
 }
 
 // device buffers of one call of the per-family entry points (uploaded on the default stream, freed on return)
@@ -127,19 +135,21 @@ struct CbDevBufs {
   }
 };
 
-// the kernel time of a call on the default stream (kernel_ms); off: every member does nothing.  Owns its two events, or borrows
-// the two a resident handle keeps.  (hidden: no symbol of the library)
+// the kernel time of a call on the default stream (kernel_ms); off: every member does nothing.  Owns its events, or borrows
+// the ones a resident handle keeps (bm: the third, for a call of two regions).  (hidden: no symbol of the library)
 struct __attribute__((visibility("hidden"))) CbKernelTimer {
   const bool on, owned;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, evm = nullptr;
+  bool lapped = false;
   explicit CbKernelTimer(bool on_) : on(on_), owned(true) {}
-  CbKernelTimer(bool on_, hipEvent_t b0, hipEvent_t b1) : on(on_), owned(false), ev0(b0), ev1(b1) {}
+  CbKernelTimer(bool on_, hipEvent_t b0, hipEvent_t b1, hipEvent_t bm = nullptr)
+      : on(on_), owned(false), ev0(b0), ev1(b1), evm(bm) {}
   CbKernelTimer(const CbKernelTimer &) = delete;
   ~CbKernelTimer() { drop(); }
   void drop() {
-    if (owned && ev0) (void)hipEventDestroy(ev0);
-    if (owned && ev1) (void)hipEventDestroy(ev1);
-    ev0 = ev1 = nullptr;
+    for (hipEvent_t e : {ev0, ev1, evm})
+      if (owned && e) (void)hipEventDestroy(e);
+    ev0 = ev1 = evm = nullptr;
   }
   // (a resident handle: once, for the borrowers of its calls)
   int create() {
@@ -156,13 +166,25 @@ struct __attribute__((visibility("hidden"))) CbKernelTimer {
     HIP_TRY(hipEventRecord(ev0, 0));
     return CB_OK;
   }
+  // the end of the first of two regions and the start of the second, with no host wait; end() then fills ms[0] and ms[1]
+  int lap() {
+    if (!on) return CB_OK;
+    if (owned) HIP_TRY(hipEventCreate(&evm));
+    HIP_TRY(hipEventRecord(evm, 0));
+    lapped = true;
+    return CB_OK;
+  }
   int end(double *ms) {
     if (!on) return CB_OK;
     float t = 0.f;
     HIP_TRY(hipEventRecord(ev1, 0));
     HIP_TRY(hipEventSynchronize(ev1));
-    HIP_TRY(hipEventElapsedTime(&t, ev0, ev1));
-    *ms = t;
+    HIP_TRY(hipEventElapsedTime(&t, ev0, lapped ? evm : ev1));
+    ms[0] = t;
+    if (lapped) {
+      HIP_TRY(hipEventElapsedTime(&t, evm, ev1));
+      ms[1] = t;
+    }
     drop();
     return CB_OK;
   }

@@ -3,26 +3,10 @@
 #include "cb_internal.hip.h"
 #include "common.hip.h"
 #include "sr.hip.h"
-#include "em_host.hip.h"
+#include "em_layout.h"
 
-namespace {
-constexpr size_t SR_MSG_BYTES = (size_t)1 << 30;   // the messages of one chunk of candidates, at most (one candidate always goes)
-
-// the bound above, or the test hook CB_SR_MSG_BYTES (cb_internal.hip.h): the results do not depend on the chunking
-size_t sr_msg_bound() {
-  const char *s = cb_test_hook("CB_SR_MSG_BYTES");
-  const long long x = s ? atoll(s) : 0;
-  return x > 0 ? (size_t)x : SR_MSG_BYTES;
-}
-
-struct SrEvents {
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  ~SrEvents() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-}  // namespace
+constexpr size_t SR_MSG_BYTES = (size_t)1 << 30;   // the messages of one chunk of candidates, at most (one candidate always goes);
+                                                   // the test hook CB_SR_MSG_BYTES: the results do not depend on the chunking
 
 extern "C" int cb_tree_site_rates(int device, int S, const double *Q, const double *pi_root, int n_fam, const int *n_nodes,
                                   const int *parent, const double *length, const int *n_units, const int8_t *codes,
@@ -72,13 +56,9 @@ extern "C" int cb_tree_site_rates(int device, int S, const double *Q, const doub
   if (ndev <= 0) return fail(CB_EHIP, "%s: no HIP device (this path has no CPU fallback)", who);
   if (device < 0 || device >= ndev) return fail(CB_EINVAL, "%s: device %d of %d", who, device, ndev);
   HIP_TRY(hipSetDevice(device));
-  const size_t SS = (size_t)S * S, msg_bound = sr_msg_bound();
+  const size_t SS = (size_t)S * S, msg_bound = cb_hook_bytes("CB_SR_MSG_BYTES", SR_MSG_BYTES);
   const int upw = 64 / S;
-  SrEvents E;
-  if (kernel_ms) {
-    kernel_ms[0] = kernel_ms[1] = 0.0;
-    for (hipEvent_t &e : E.ev) HIP_TRY(hipEventCreate(&e));
-  }
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.0;
   // the library's own GENERAL expm, counts-free, as cb_bl_create builds its banks: one handle for the call.  (The expm of the
   // symmetric eigendecomposition is far faster on n_nodes x n_cands matrices but misses the scan's accuracy at very long edges:
   // DESIGN.md section 17.)
@@ -114,11 +94,13 @@ extern "C" int cb_tree_site_rates(int device, int S, const double *Q, const doub
     int *dcur = current ? bufs.up(current + off_u[f], U, rc) : nullptr, *dbest = bufs.up<int>(nullptr, U, rc);
     const int8_t *dcodes = bufs.up(codes + off_c[f], (size_t)n * U, rc);
     if (rc != CB_OK) break;
-    if (kernel_ms && hipEventRecord(E.ev[0], 0) != hipSuccess) rc = fail(CB_EHIP, "%s: hipEventRecord failed", who);
+    CbKernelTimer timer(kernel_ms != nullptr);   // (bank, scan + pick) of this family
+    double ms[2] = {0.0, 0.0};
+    rc = timer.begin(false);
     if (rc == CB_OK) rc = cb_internal_set_times(hexp, times.data(), n * C, nullptr);
     if (rc == CB_OK) rc = cb_internal_expm_bank(hexp, dQ, nullptr, CB_PTR_DEVICE | CB_NO_SYNC, dP);
+    if (rc == CB_OK) rc = timer.lap();
     if (rc != CB_OK) break;
-    if (kernel_ms && hipEventRecord(E.ev[1], 0) != hipSuccess) rc = fail(CB_EHIP, "%s: hipEventRecord failed", who);
     SrScanArgs a{};
     a.S = S; a.n_units = U; a.n_cands = C; a.root = F.root; a.n_blocks = n_blocks;
     a.child_ptr = dcp; a.child_idx = dci; a.P = dP; a.codes = reinterpret_cast<const signed char *>(dcodes); a.pi_root = dpi;
@@ -137,19 +119,11 @@ extern "C" int cb_tree_site_rates(int device, int S, const double *Q, const doub
     p.ll = dll; p.best = dbest; p.best_ll = dbest_ll;
     hipLaunchKernelGGL(sr_pick_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, 0, p);
     if (rc == CB_OK && hipGetLastError() != hipSuccess) rc = fail(CB_EHIP, "%s: family %d: a kernel launch failed", who, f);
+    if (rc == CB_OK) rc = timer.end(ms);
     if (rc != CB_OK) break;
     if (kernel_ms) {
-      float ms0 = 0.f, ms1 = 0.f;
-      hipError_t e = hipEventRecord(E.ev[2], 0);
-      if (e == hipSuccess) e = hipEventSynchronize(E.ev[2]);
-      if (e == hipSuccess) e = hipEventElapsedTime(&ms0, E.ev[0], E.ev[1]);
-      if (e == hipSuccess) e = hipEventElapsedTime(&ms1, E.ev[1], E.ev[2]);
-      if (e != hipSuccess) {
-        rc = fail(CB_EHIP, "%s: %s", who, hipGetErrorString(e));
-        break;
-      }
-      kernel_ms[0] += ms0;
-      kernel_ms[1] += ms1;
+      kernel_ms[0] += ms[0];
+      kernel_ms[1] += ms[1];
     }
     hipError_t e = hipMemcpy(best + off_u[f], dbest, (size_t)U * sizeof(int), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(best_ll + off_u[f], dbest_ll, (size_t)U * sizeof(double), hipMemcpyDeviceToHost);

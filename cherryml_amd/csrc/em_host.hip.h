@@ -1,133 +1,121 @@
-// Host side of the tree EM handles (cb_em.hip, cb_bl.hip): the quantisation rule, one family's validation and host-side
-// structures, and the model check.  No device work; `who` names the entry point in the messages.
+// Device side of the tree EM handles (cb_em.hip, cb_bl.hip): the forest's resident buffers, a family's view of them, the inside
+// and outside passes and the way back of l_u.  The host side (validation, layout, unit order) is em_layout.h.
 #pragma once
 #include "cb_internal.hip.h"
+#include "em_layout.h"
+#include "em_shared.hip.h"
 
-namespace {
-// the reference's quantisation rule (cherryml/utils.py:35-56, counting.hip.h cnt_quantize), clamped to the grid's ends:
-// every edge of the tree needs a transition matrix
-int em_quantize(double t, const double *grid, int B) {
-  if (!(t > grid[0])) return 0;
-  if (t >= grid[B - 1]) return B - 1;
-  const int lo = int(std::lower_bound(grid, grid + B, t) - grid);
-  const double rel_left = t / grid[lo - 1] - 1.0, rel_right = grid[lo] / t - 1.0;
-  return rel_left < rel_right ? lo - 1 : lo;
-}
-
-struct EmFamHost {
-  int n_nodes = 0, n_units = 0, n_cats = 0, root = -1;
-  std::vector<int> child_ptr, child_idx, level_ptr, level_nodes, depth_ptr, depth_nodes, perm, unit_cat, cat_ptr, qb;
-  std::vector<double> cats;   // the distinct site rates, ascending
-};
-}  // namespace
-
-// validation and the host-side structures of one family (no device work)
-static int em_prepare(const char *who, int S, int B, const double *grid, int n, const int *parent, const double *length, int U,
-                      const double *rate, const int8_t *codes, int f, EmFamHost &F) {
-  if (n < 1 || U < 1) return fail(CB_EINVAL, "%s: family %d has bad sizes (nodes = %d, units = %d)", who, f, n, U);
-  F.n_nodes = n;
-  F.n_units = U;
-  std::vector<int> nchild(n, 0);
-  for (int v = 0; v < n; ++v) {
-    const int p = parent[v];
-    if (p == -1) {
-      if (F.root >= 0) return fail(CB_EINVAL, "%s: family %d has two roots (%d and %d)", who, f, F.root, v);
-      F.root = v;
-    } else if (p < 0 || p >= n || p == v) {
-      return fail(CB_EINVAL, "%s: family %d: parent[%d] = %d", who, f, v, p);
-    } else {
-      nchild[p]++;
-      if (!(length[v] >= 0.0) || !std::isfinite(length[v]))
-        return fail(CB_EINVAL, "%s: family %d: length[%d] = %g", who, f, v, length[v]);
-    }
-  }
-  if (F.root < 0) return fail(CB_EINVAL, "%s: family %d has no root (parent -1)", who, f);
-  F.child_ptr.assign(n + 1, 0);
-  for (int v = 0; v < n; ++v) F.child_ptr[v + 1] = F.child_ptr[v] + nchild[v];
-  F.child_idx.assign(std::max(n - 1, 1), 0);
-  std::vector<int> fill(n, 0);
-  for (int v = 0; v < n; ++v)
-    if (parent[v] >= 0) F.child_idx[F.child_ptr[parent[v]] + fill[parent[v]]++] = v;
-  // depths from the root (breadth first): every node reached exactly once <=> the parent array is a tree
-  std::vector<int> depth(n, -1), order;
-  order.reserve(n);
-  order.push_back(F.root);
-  depth[F.root] = 0;
-  for (size_t i = 0; i < order.size(); ++i) {
-    const int v = order[i];
-    for (int c = F.child_ptr[v]; c < F.child_ptr[v + 1]; ++c) {
-      depth[F.child_idx[c]] = depth[v] + 1;
-      order.push_back(F.child_idx[c]);
-    }
-  }
-  if ((int)order.size() != n) return fail(CB_EINVAL, "%s: family %d: the parent array is not a tree (a cycle)", who, f);
-  std::vector<int> height(n, 0);
-  for (int i = n - 1; i > 0; --i) height[parent[order[i]]] = std::max(height[parent[order[i]]], height[order[i]] + 1);
-  const int nh = height[F.root] + 1;
-  F.level_ptr.assign(nh + 1, 0);
-  for (int v = 0; v < n; ++v) F.level_ptr[height[v] + 1]++;
-  for (int l = 0; l < nh; ++l) F.level_ptr[l + 1] += F.level_ptr[l];
-  F.level_nodes.assign(n, 0);
-  {
-    std::vector<int> at(F.level_ptr.begin(), F.level_ptr.end() - 1);
-    for (int v = 0; v < n; ++v) F.level_nodes[at[height[v]]++] = v;
-  }
-  // internal non-root nodes by depth (the outside pass)
-  int nd = 0;
-  for (int v = 0; v < n; ++v) nd = std::max(nd, depth[v] + 1);
-  F.depth_ptr.assign(nd + 1, 0);
-  for (int v = 0; v < n; ++v)
-    if (v != F.root && nchild[v] > 0) F.depth_ptr[depth[v] + 1]++;
-  for (int l = 0; l < nd; ++l) F.depth_ptr[l + 1] += F.depth_ptr[l];
-  F.depth_nodes.assign(std::max(F.depth_ptr[nd], 1), 0);
-  {
-    std::vector<int> at(F.depth_ptr.begin(), F.depth_ptr.end() - 1);
-    for (int v : order)
-      if (v != F.root && nchild[v] > 0) F.depth_nodes[at[depth[v]]++] = v;
-  }
-  // rate categories (distinct rates, ascending) and the units sorted by category (stable)
-  std::vector<double> cats(rate, rate + U);
-  for (int u = 0; u < U; ++u)
-    if (!(rate[u] >= 0.0) || !std::isfinite(rate[u])) return fail(CB_EINVAL, "%s: family %d: site rate %d = %g", who, f, u, rate[u]);
-  std::sort(cats.begin(), cats.end());
-  cats.erase(std::unique(cats.begin(), cats.end()), cats.end());
-  F.n_cats = (int)cats.size();
-  F.cats = cats;
-  std::vector<int> ucat(U);
-  for (int u = 0; u < U; ++u) ucat[u] = int(std::lower_bound(cats.begin(), cats.end(), rate[u]) - cats.begin());
-  F.perm.resize(U);
-  for (int u = 0; u < U; ++u) F.perm[u] = u;
-  std::stable_sort(F.perm.begin(), F.perm.end(), [&](int x, int y) { return ucat[x] < ucat[y]; });
-  F.unit_cat.resize(U);
-  F.cat_ptr.assign(F.n_cats + 1, 0);
-  for (int k = 0; k < U; ++k) {
-    F.unit_cat[k] = ucat[F.perm[k]];
-    F.cat_ptr[F.unit_cat[k] + 1]++;
-  }
-  for (int c = 0; c < F.n_cats; ++c) F.cat_ptr[c + 1] += F.cat_ptr[c];
-  F.qb.assign((size_t)n * F.n_cats, 0);
-  for (int v = 0; v < n; ++v)
-    if (v != F.root)
-      for (int c = 0; c < F.n_cats; ++c) F.qb[(size_t)v * F.n_cats + c] = em_quantize(length[v] * cats[c], grid, B);
-  for (int v = 0; v < n; ++v)
-    if (!nchild[v])
-      for (int u = 0; u < U; ++u)
-        if (codes[(size_t)v * U + u] >= S || codes[(size_t)v * U + u] < -1)
-          return fail(CB_EINVAL, "%s: family %d: state code %d out of range [-1, S) at node %d unit %d", who, f,
-                      (int)codes[(size_t)v * U + u], v, u);
+// what a create does before its first allocation: a device, `device` among them, the current one
+static int em_open_device(const char *who, int device) {
+  const int ndev = cb_device_count();
+  if (ndev <= 0) return fail(CB_EHIP, "%s: no HIP device (this path has no CPU fallback)", who);
+  if (device < 0 || device >= ndev) return fail(CB_EINVAL, "%s: device %d of %d", who, device, ndev);
+  if (hipSetDevice(device) != hipSuccess) return fail(CB_EHIP, "%s: hipSetDevice(%d) failed", who, device);
   return CB_OK;
 }
 
-// a rate matrix (finite, off-diagonal >= 0) and a root distribution (finite, >= 0, positive sum)
-static int em_check_model(const char *who, int S, const double *Q, const double *pi_root) {
-  double psum = 0.0;
-  for (int i = 0; i < S; ++i) {
-    if (!(pi_root[i] >= 0.0) || !std::isfinite(pi_root[i])) return fail(CB_EINVAL, "%s: pi_root[%d] = %g", who, i, pi_root[i]);
-    psum += pi_root[i];
-    for (int j = 0; j < S; ++j)
-      if (!std::isfinite(Q[i * S + j]) || (i != j && Q[i * S + j] < 0.0))
-        return fail(CB_EINVAL, "%s: Q[%d][%d] = %g", who, i, j, Q[i * S + j]);
+// family f of a forest on the device: where each of its arrays starts
+struct EmFamView {
+  const EmFamHost &F;
+  int n_blocks;   // site tiles of a launch: 64 / S units per wave
+  int *parent, *child_ptr, *child_idx, *level_nodes, *depth_nodes, *qb, *unit_cat;
+  signed char *codes;   // [node][unit]
+  double *msg, *U;      // [node][unit][S]
+  double *ll;           // [unit]
+};
+
+struct EmForest {
+  int device = 0, S = 0;
+  EmForestHost host;
+  std::vector<void *> bufs;   // every device buffer of the handle, the owner's own included
+  int *dparent = nullptr, *dcp = nullptr, *dci = nullptr, *dlev = nullptr, *ddep = nullptr, *dqb = nullptr, *duc = nullptr;
+  signed char *dcodes = nullptr;
+  double *dmsg = nullptr, *dU = nullptr, *dll = nullptr;
+
+  // `count` elements (at least one), from `src` when not null; after a failure (rc) it does nothing
+  template <typename T>
+  T *alloc(const char *who, const T *src, size_t count, int &rc) {
+    if (rc != CB_OK) return nullptr;
+    void *p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
+      (void)hipGetLastError();
+      rc = fail(CB_ENOMEM, "%s: %zu bytes of device memory", who, count * sizeof(T));
+      return nullptr;
+    }
+    bufs.push_back(p);
+    if (src && count && hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
+      rc = fail(CB_EHIP, "%s: upload failed", who);
+    return static_cast<T *>(p);
   }
-  if (!(psum > 0.0)) return fail(CB_EINVAL, "%s: pi_root sums to %g", who, psum);
+  // the host's arrays, and the messages and l_u of all families
+  void upload(const char *who, int &rc) {
+    const size_t NU = host.off_c.back();
+    dmsg = alloc<double>(who, nullptr, NU * S, rc);
+    dU = alloc<double>(who, nullptr, NU * S, rc);
+    dll = alloc<double>(who, nullptr, host.off_u.back(), rc);
+    dparent = alloc(who, host.parent.data(), host.parent.size(), rc);
+    dcp = alloc(who, host.child_ptr.data(), host.child_ptr.size(), rc);
+    dci = alloc(who, host.child_idx.data(), host.child_idx.size(), rc);
+    dlev = alloc(who, host.level_nodes.data(), host.level_nodes.size(), rc);
+    ddep = alloc(who, host.depth_nodes.data(), host.depth_nodes.size(), rc);
+    dqb = alloc(who, host.qb.data(), host.qb.size(), rc);
+    duc = alloc(who, host.unit_cat.data(), host.unit_cat.size(), rc);
+    dcodes = reinterpret_cast<signed char *>(alloc(who, host.codes.data(), NU, rc));
+  }
+  void free_all() {
+    for (void *p : bufs)
+      if (p) (void)hipFree(p);
+    bufs.clear();
+  }
+  EmFamView view(int f) const {
+    const EmFamHost &F = host.fam[f];
+    const size_t on = host.off_n[f], oc = host.off_c[f];
+    const int upw = 64 / S;
+    return EmFamView{F, (F.n_units + upw - 1) / upw, dparent + on, dcp + on + f, dci + on, dlev + on, ddep + host.off_dep[f],
+                     dqb + host.off_q[f], duc + host.off_u[f], dcodes + oc, dmsg + oc * S, dU + oc * S, dll + host.off_u[f]};
+  }
+};
+
+// the inside pass of family f (and its outside pass) with the bank P and the root distribution, stream 0
+static void em_launch_passes(const EmForest &T, int f, const double *P, const double *pi_root, bool outside) {
+  const EmFamView w = T.view(f);
+  const EmFamHost &F = w.F;
+  TlArgs a{};
+  a.S = T.S; a.S1 = 0; a.n_nodes = F.n_nodes; a.n_units = F.n_units; a.NU = F.n_units; a.root = F.root; a.n_blocks = w.n_blocks;
+  a.child_ptr = w.child_ptr; a.child_idx = w.child_idx; a.P = P; a.unit_cat = w.unit_cat; a.code_a = w.codes; a.code_b = nullptr;
+  a.pi_root = pi_root; a.msg = w.msg; a.ll = w.ll;
+  for (size_t l = 0; l + 1 < F.level_ptr.size(); ++l) {
+    TlArgs b = a;
+    b.level_nodes = w.level_nodes + F.level_ptr[l];
+    b.n_level = F.level_ptr[l + 1] - F.level_ptr[l];
+    em_launch_up(b, w.qb, F.n_cats, (unsigned)(b.n_level * w.n_blocks));
+  }
+  if (!outside) return;
+  EmDownArgs d{};
+  d.S = T.S; d.n_units = F.n_units; d.root = F.root; d.n_blocks = w.n_blocks; d.n_cats = F.n_cats;
+  d.parent = w.parent; d.child_ptr = w.child_ptr; d.child_idx = w.child_idx; d.qb = w.qb; d.unit_cat = w.unit_cat; d.P = P;
+  d.pi_root = pi_root; d.msg = w.msg; d.U = w.U;
+  for (size_t l = 0; l + 1 < F.depth_ptr.size(); ++l) {
+    const int nl = F.depth_ptr[l + 1] - F.depth_ptr[l];
+    if (nl == 0) continue;
+    EmDownArgs e = d;
+    e.level_nodes = w.depth_nodes + F.depth_ptr[l];
+    em_launch_down(e, (unsigned)(nl * w.n_blocks));
+  }
+}
+
+// l_u of the device (category order) -> orig, the caller's unit order; fam_ll (or null) takes the sums of the families in `which`
+// (null: of all), in the caller's order
+static int em_read_ll(const EmForest &T, const char *which, std::vector<double> &orig, double *fam_ll) {
+  const size_t n = T.host.off_u.back();
+  std::vector<double> llp(n);
+  orig.resize(n);
+  HIP_TRY(hipMemcpy(llp.data(), T.dll, n * sizeof(double), hipMemcpyDeviceToHost));
+  for (int f = 0; f < T.host.n_fam(); ++f) {
+    const EmFamHost &F = T.host.fam[f];
+    const size_t ub = T.host.off_u[f];
+    em_unpermute(F.perm, llp.data() + ub, orig.data() + ub);
+    if (fam_ll && (!which || which[f])) fam_ll[f] = em_family_ll(orig.data() + ub, F.n_units);
+  }
   return CB_OK;
 }

@@ -20,37 +20,25 @@ from .. import _lib, caching
 DEFAULT_GRID = [0.03 * 1.1 ** i for i in range(-64, 65)]   # the reference pipeline's grid (center 0.03, step 1.1, +-64)
 
 
-class EStep:
+class EStep(_lib.ResidentHandle):
     """The E-step resident on one GPU: trees, leaf codes, site-rate categories and the accumulation's task lists are uploaded
     once (`cb_em_create`); each `expected_counts(Q, pi_root)` sends only Q and pi_root.
 
     trees: `io.Tree`s; leaf_codes: per family an int8 array [n_nodes, n_sites] with rows in `tree.nodes()` order (-1 = gap;
     only leaf rows are read); site_rates: per family [n_sites]; grid: the quantisation points (increasing).  A context
     manager; `close()` frees the handle."""
+    _destroy = "cb_em_destroy"
 
     def __init__(self, trees: Sequence, leaf_codes: Sequence[np.ndarray], site_rates: Sequence, grid: Sequence[float],
                  device: Optional[int] = None, num_states: int = 20):
         from ..counting._stage import _device_index
-        from ..evaluation._likelihood import _tree_arrays
-        self._h = None
+        from ..evaluation._likelihood import _pack_forest
         self.grid = np.ascontiguousarray(np.asarray(grid, dtype=np.float64).reshape(-1))
         if len(trees) == 0 or len(trees) != len(leaf_codes) or len(trees) != len(site_rates):
             raise ValueError("EStep: need one tree, one code array and one site-rate vector per family (at least one family)")
-        n_nodes, n_units, parent, length, rates, codes = [], [], [], [], [], []
         self.S = None
-        for tree, c, r in zip(trees, leaf_codes, site_rates):
-            _, _, par, ln = _tree_arrays(tree)
-            c = np.ascontiguousarray(c, dtype=np.int8)
-            r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
-            if c.ndim != 2 or c.shape[0] != par.size or c.shape[1] != r.size:
-                raise ValueError("EStep: codes must be [n_nodes, n_sites] and site_rates [n_sites]")
-            n_nodes.append(par.size), n_units.append(r.size)
-            parent.append(par), length.append(ln), rates.append(r), codes.append(c.reshape(-1))
-        self.n_nodes = np.array(n_nodes, dtype=np.int32)
-        self.n_units = np.array(n_units, dtype=np.int32)
-        self._n_edges_sites = int(sum((n - 1) * u for n, u in zip(n_nodes, n_units)))
-        self._args = [np.ascontiguousarray(np.concatenate(x), dtype=dt) for x, dt in
-                      ((parent, np.int32), (length, np.float64), (rates, np.float64), (codes, np.int8))]
+        self.n_nodes, self.n_units, *self._args = _pack_forest("EStep", trees, leaf_codes, site_rates)
+        self._n_edges_sites = int(sum((int(n) - 1) * int(u) for n, u in zip(self.n_nodes, self.n_units)))
         self.device = _device_index() if device is None else int(device)
         self.last_kernel_ms = 0.0
         self.last_unit_loglik: Optional[List[np.ndarray]] = None
@@ -79,38 +67,20 @@ class EStep:
         S = Q.shape[0]
         if Q.shape != (S, S) or pi.shape != (S,):
             raise ValueError(f"EStep: Q must be square and pi_root of its size: {Q.shape}, {pi.shape}")
-        if self._h is None:
-            raise _lib.CherryBankError("EStep is closed")
+        h = self._handle()
         if S != self.S:
             raise ValueError(f"EStep: made for {self.S} states, got {S}")
         E = np.empty((self.grid.size, S, S))
         ll = np.empty(int(self.n_units.sum()))
         fam = np.empty(self.n_nodes.size)
         ms = ctypes.c_double(0.0)
-        rc = _lib.load().cb_em_estep(self._h, Q.ctypes.data, pi.ctypes.data, E.ctypes.data, ll.ctypes.data, fam.ctypes.data,
+        rc = _lib.load().cb_em_estep(h, Q.ctypes.data, pi.ctypes.data, E.ctypes.data, ll.ctypes.data, fam.ctypes.data,
                                      ctypes.byref(ms))
         _lib.check(rc, "cb_em_estep")
         self.last_kernel_ms = ms.value
         self.last_unit_loglik = np.split(ll, np.cumsum(self.n_units)[:-1])
         self.last_family_loglik = fam
         return E, float(fam.sum())
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            _lib.load().cb_em_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def m_step(grid: np.ndarray, E: np.ndarray, Q: np.ndarray, num_epochs: int, learning_rate: float, device: int) -> np.ndarray:

@@ -54,6 +54,29 @@ def _tree_arrays(tree: Tree):
     return out
 
 
+def _pack_forest(who: str, trees, leaf_codes, site_rates):
+    """(trees, per-family codes [n_nodes, n_sites], per-family site rates or None) -> n_nodes, n_units (int32 per family) and the
+    concatenated parent (int32), length, rates (float64; None without site rates) and codes (int8) the tree EM entry points
+    (cb_em_create, cb_bl_create, cb_tree_site_rates) take; `who` names the caller in the messages"""
+    n_nodes, n_units, parent, length, rates, codes = [], [], [], [], [], []
+    for f, (tree, c) in enumerate(zip(trees, leaf_codes)):
+        _, _, par, ln = _tree_arrays(tree)
+        c = np.ascontiguousarray(c, dtype=np.int8)
+        if site_rates is None:
+            if c.ndim != 2 or c.shape[0] != par.size or c.shape[1] < 1:
+                raise ValueError(f"{who}: family {f}: codes must be [n_nodes, n_sites] (got {c.shape} for {par.size} nodes)")
+        else:
+            r = np.ascontiguousarray(site_rates[f], dtype=np.float64).reshape(-1)
+            if c.ndim != 2 or c.shape[0] != par.size or c.shape[1] != r.size:
+                raise ValueError(f"{who}: codes must be [n_nodes, n_sites] and site_rates [n_sites]")
+            rates.append(r)
+        n_nodes.append(par.size), n_units.append(c.shape[1])
+        parent.append(par), length.append(ln), codes.append(c.reshape(-1))
+    cat = lambda xs, dt: np.ascontiguousarray(np.concatenate(xs), dtype=dt)   # noqa: E731
+    return (np.array(n_nodes, dtype=np.int32), np.array(n_units, dtype=np.int32), cat(parent, np.int32), cat(length, np.float64),
+            None if site_rates is None else cat(rates, np.float64), cat(codes, np.int8))
+
+
 def _family_arrays(trees: List[Tree], codes_a, codes_b, unit_rates):
     """the concatenated per-family arrays cb_tl_model_run / cb_tree_likelihood_batch take"""
     pairs = codes_b is not None

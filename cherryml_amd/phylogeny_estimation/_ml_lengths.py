@@ -27,7 +27,7 @@ from ._fast_cherries import quantization_points_ble
 DEFAULT_MAX_BANK_BYTES = 4 << 30   # banks (P and log P) of the families of one handle, at most
 
 
-class BranchLengthFitter:
+class BranchLengthFitter(_lib.ResidentHandle):
     """Branch-length EM resident on one GPU: trees, leaf codes, site-rate categories and each family's bank of
     expm(grid[tau] rate_c Q) and its logarithm are built once (`cb_bl_create`); `round()` is one EM step for all families.
 
@@ -35,12 +35,12 @@ class BranchLengthFitter:
     [n_nodes, n_sites] with rows in `tree.nodes()` order (-1 = gap; only leaf rows are read); site_rates: per family [n_sites],
     finite and > 0; grid: the T >= 2 grid points (increasing); Q [S, S], pi_root [S], 2 <= S <= 32.  A context manager;
     `close()` frees the handle."""
+    _destroy = "cb_bl_destroy"
 
     def __init__(self, trees: Sequence, leaf_codes: Sequence[np.ndarray], site_rates: Sequence, grid: Sequence[float], Q, pi_root,
                  device: Optional[int] = None):
         from ..counting._stage import _device_index
-        from ..evaluation._likelihood import _tree_arrays
-        self._h = None
+        from ..evaluation._likelihood import _pack_forest
         self.grid = np.ascontiguousarray(np.asarray(grid, dtype=np.float64).reshape(-1))
         self.Q = np.ascontiguousarray(Q, dtype=np.float64)
         self.pi_root = np.ascontiguousarray(pi_root, dtype=np.float64).reshape(-1)
@@ -50,25 +50,12 @@ class BranchLengthFitter:
         if len(trees) == 0 or len(trees) != len(leaf_codes) or len(trees) != len(site_rates):
             raise ValueError("BranchLengthFitter: need one tree, one code array and one site-rate vector per family "
                              "(at least one family)")
-        n_nodes, n_units, parent, length, rates, codes = [], [], [], [], [], []
-        self._nodes: List[List[str]] = []
-        for tree, c, r in zip(trees, leaf_codes, site_rates):
-            _, _, par, ln = _tree_arrays(tree)
-            c = np.ascontiguousarray(c, dtype=np.int8)
-            r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
-            if c.ndim != 2 or c.shape[0] != par.size or c.shape[1] != r.size:
-                raise ValueError("BranchLengthFitter: codes must be [n_nodes, n_sites] and site_rates [n_sites]")
-            n_nodes.append(par.size), n_units.append(r.size)
-            parent.append(par), length.append(ln), rates.append(r), codes.append(c.reshape(-1))
-            self._nodes.append(list(tree.nodes()))
+        self.n_nodes, self.n_units, *self._args = _pack_forest("BranchLengthFitter", trees, leaf_codes, site_rates)
+        self._nodes: List[List[str]] = [list(tree.nodes()) for tree in trees]
         self.S = S
-        self.n_nodes = np.array(n_nodes, dtype=np.int32)
-        self.n_units = np.array(n_units, dtype=np.int32)
-        self._args = [np.ascontiguousarray(np.concatenate(x), dtype=dt) for x, dt in
-                      ((parent, np.int32), (length, np.float64), (rates, np.float64), (codes, np.int8))]
         self.device = _device_index() if device is None else int(device)
         self.last_kernel_ms = (0.0, 0.0)   # (passes, M-step) of the last round
-        self._parent = [np.asarray(p, dtype=np.int32) for p in parent]
+        self._parent = np.split(self._args[0], np.cumsum(self.n_nodes)[:-1])
         self.last_nni_kernel_ms = (0.0, 0.0)   # (passes, scan) of the last nni_scan
         self.last_ancestral_kernel_ms = (0.0, 0.0)   # (passes, reconstruction) of the last ancestral_states
         self._create()
@@ -81,11 +68,6 @@ class BranchLengthFitter:
                                       ln.ctypes.data, self.n_units.ctypes.data, rt.ctypes.data, cd.ctypes.data, ctypes.byref(h))
         _lib.check(rc, "cb_bl_create")
         self._h = h
-
-    def _handle(self):
-        if self._h is None:
-            raise _lib.CherryBankError("BranchLengthFitter is closed")
-        return self._h
 
     def round(self) -> Tuple[np.ndarray, np.ndarray]:
         """One EM step -> (n_changed [n_fam], fam_ll [n_fam]): the indices the round changed and every family's log-likelihood
@@ -179,23 +161,6 @@ class BranchLengthFitter:
         if not posteriors:
             return states, confs
         return states, confs, [x.reshape(sh + (self.S,)) for x, sh in zip(np.split(post, cuts * self.S), shapes)]
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None:
-            _lib.load().cb_bl_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _batches(bank_bytes: Sequence[int], bound: int) -> List[List[int]]:

@@ -54,7 +54,7 @@ def tree_site_rates(trees: Sequence, leaf_codes: Sequence[np.ndarray], candidate
     keeps it, and a site with fewer than two observed leaves always does (candidate 0 without one); Q [S, S], pi_root [S],
     2 <= S <= 32.  profile: a dict that receives `bank_kernel_ms` and `scan_kernel_ms`."""
     from ..counting._stage import _device_index
-    from ..evaluation._likelihood import _tree_arrays
+    from ..evaluation._likelihood import _pack_forest
     Q = np.ascontiguousarray(Q, dtype=np.float64)
     pi_root = np.ascontiguousarray(pi_root, dtype=np.float64).reshape(-1)
     S = Q.shape[0]
@@ -70,28 +70,23 @@ def tree_site_rates(trees: Sequence, leaf_codes: Sequence[np.ndarray], candidate
         candidates = [candidates] * n_fam
     if len(candidates) != n_fam:
         raise ValueError(f"tree_site_rates: {len(candidates)} candidate lists for {n_fam} families")
-    n_nodes, n_units, n_cands, parent, length, codes, cands, cur = [], [], [], [], [], [], [], []
-    for f, (tree, c, cd) in enumerate(zip(trees, leaf_codes, candidates)):
-        _, _, par, ln = _tree_arrays(tree)
-        c = np.ascontiguousarray(c, dtype=np.int8)
+    n_nodes, n_units, parent, length, _, codes = _pack_forest("tree_site_rates", trees, leaf_codes, None)
+    cands, cur = [], []
+    for f, cd in enumerate(candidates):
         cd = np.asarray(cd, dtype=np.float64)
-        if c.ndim != 2 or c.shape[0] != par.size or c.shape[1] < 1:
-            raise ValueError(f"tree_site_rates: family {f}: codes must be [n_nodes, n_sites] (got {c.shape} for {par.size} nodes)")
         if cd.ndim != 1 or cd.size < 1:
             raise ValueError(f"tree_site_rates: family {f}: candidates must be a non-empty list of rates")
         if current is not None:
             k = np.asarray(current[f])
-            if k.shape != (c.shape[1],) or not np.issubdtype(k.dtype, np.integer):
+            if k.shape != (n_units[f],) or not np.issubdtype(k.dtype, np.integer):
                 raise ValueError(f"tree_site_rates: family {f}: current must be [n_sites] integer indices (got {k.shape}, {k.dtype})")
             cur.append(k)
-        n_nodes.append(par.size), n_units.append(c.shape[1]), n_cands.append(cd.size)
-        parent.append(par), length.append(ln), codes.append(c.reshape(-1)), cands.append(cd)
-    n_nodes, n_units, n_cands = (np.array(x, dtype=np.int32) for x in (n_nodes, n_units, n_cands))
+        cands.append(cd)
+    n_cands = np.array([cd.size for cd in cands], dtype=np.int32)
     cat = lambda xs, dt: np.ascontiguousarray(np.concatenate(xs), dtype=dt)   # noqa: E731
     device = _device_index() if device is None else int(device)
-    best, best_ll, ll_all, ms = _scan(device, S, Q, pi_root, n_nodes, cat(parent, np.int32), cat(length, np.float64), n_units,
-                                      cat(codes, np.int8), n_cands, cat(cands, np.float64),
-                                      cat(cur, np.int32) if current is not None else None, bool(return_all))
+    best, best_ll, ll_all, ms = _scan(device, S, Q, pi_root, n_nodes, parent, length, n_units, codes, n_cands,
+                                      cat(cands, np.float64), cat(cur, np.int32) if current is not None else None, bool(return_all))
     if profile is not None:
         profile["bank_kernel_ms"], profile["scan_kernel_ms"] = ms
     cut = np.cumsum(n_units)[:-1]
