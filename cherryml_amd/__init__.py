@@ -11,6 +11,7 @@ from .phylogeny_estimation import BranchLengthFitter, fast_cherries, ml_branch_l
 from .phylogeny_estimation import ml_lengths_and_site_rates, ml_site_rates, nj_ml_rates_trees, tree_site_rates  # noqa: F401,E402
 from .phylogeny_estimation import apply_nni, ml_nni_trees, nj_nni_trees, select_nni  # noqa: F401,E402
 from .phylogeny_estimation import ml_ancestral_sequences  # noqa: F401,E402
+from .phylogeny_estimation import ml_branch_supports  # noqa: F401,E402
 from ._cherryml_public_api import cherryml_public_api  # noqa: F401,E402
 from .simulation import simulate_msas  # noqa: F401,E402
 from .estimation import (EStep, RateMatrix, RateMatrixLearner, em_lg, jtt_ipw, quantized_transitions_mle,  # noqa: F401
@@ -26,5 +27,5 @@ __all__ = [
     "EStep", "em_lg", "lg_end_to_end_with_em_optimizer", "nj_trees",
     "BranchLengthFitter", "ml_branch_lengths", "nj_ml_trees",
     "tree_site_rates", "ml_site_rates", "ml_lengths_and_site_rates", "nj_ml_rates_trees",
-    "apply_nni", "select_nni", "ml_nni_trees", "nj_nni_trees", "ml_ancestral_sequences",
+    "apply_nni", "select_nni", "ml_nni_trees", "nj_nni_trees", "ml_ancestral_sequences", "ml_branch_supports",
 ]

@@ -1,11 +1,13 @@
 // libcherrybank: maximum-likelihood branch lengths on fixed trees by EM, on a resident handle (bl.hip.h; include/cherrybank.h,
 // cb_bl_*), the nearest-neighbour-interchange scan on the handle's resident messages (nni.hip.h; cb_bl_nni_scan) and the marginal
-// ancestral reconstruction from the same messages (anc.hip.h; cb_bl_ancestral).
+// ancestral reconstruction from the same messages (anc.hip.h; cb_bl_ancestral) and the local branch supports by resampling the
+// scan's per-site log-likelihoods (sup.hip.h; cb_bl_supports).
 #include "cb_internal.hip.h"
 #include "common.hip.h"
 #include "bl.hip.h"
 #include "nni.hip.h"
 #include "anc.hip.h"
+#include "sup.hip.h"
 #include "em_host.hip.h"
 
 struct cb_bl_s {
@@ -215,6 +217,26 @@ extern "C" int cb_bl_get(cb_bl_s *h, int *index, double *ll, double *fam_ll) {
   return CB_OK;
 }
 
+// the triples of family f, on the host: what cb_bl_nni_scan and cb_bl_supports refuse, in these words
+static int bl_check_moves(const char *who, const EmForestHost &H, int f, int n_moves, const int *moves) {
+  const EmFamHost &F = H.fam[f];
+  const int n = F.n_nodes, *par = H.parent.data() + H.off_n[f];
+  for (int m = 0; m < n_moves; ++m) {
+    const int *t = moves + 3 * (size_t)m;
+    const int v = t[0], c = t[1], s = t[2];
+    if (v < 0 || v >= n) return fail(CB_EINVAL, "%s: family %d move %d: v = %d (0 <= index < %d)", who, f, m, v, n);
+    if (c < 0 || c >= n) return fail(CB_EINVAL, "%s: family %d move %d: c = %d (0 <= index < %d)", who, f, m, c, n);
+    if (s < 0 || s >= n) return fail(CB_EINVAL, "%s: family %d move %d: s = %d (0 <= index < %d)", who, f, m, s, n);
+    if (v == F.root) return fail(CB_EINVAL, "%s: family %d move %d: v = %d is the root", who, f, m, v);
+    if (F.child_ptr[v] == F.child_ptr[v + 1]) return fail(CB_EINVAL, "%s: family %d move %d: v = %d is a leaf", who, f, m, v);
+    if (par[c] != v) return fail(CB_EINVAL, "%s: family %d move %d: c = %d is not a child of v = %d", who, f, m, c, v);
+    if (s == v) return fail(CB_EINVAL, "%s: family %d move %d: s = %d equals v", who, f, m, s);
+    if (par[s] != par[v])
+      return fail(CB_EINVAL, "%s: family %d move %d: s = %d is not a child of parent[v] = %d", who, f, m, s, par[v]);
+  }
+  return CB_OK;
+}
+
 constexpr size_t NNI_LL_BYTES = (size_t)256 << 20;   // ll'[move][unit] of one chunk of moves, at most (one move always goes); the
                                                      // test hook CB_NNI_LL_BYTES: the results do not depend on the chunking
 
@@ -238,20 +260,8 @@ extern "C" int cb_bl_nni_scan(cb_bl_s *h, const int *n_moves, const int *moves, 
   const size_t bound = cb_hook_bytes("CB_NNI_LL_BYTES", NNI_LL_BYTES);
   for (int f = 0; f < n_fam; ++f) {
     const EmFamHost &F = H.fam[f];
-    const int n = F.n_nodes, *par = H.parent.data() + H.off_n[f];
-    for (int m = 0; m < n_moves[f]; ++m) {
-      const int *t = moves + 3 * (off_m[f] + m);
-      const int v = t[0], c = t[1], s = t[2];
-      if (v < 0 || v >= n) return fail(CB_EINVAL, "%s: family %d move %d: v = %d (0 <= index < %d)", who, f, m, v, n);
-      if (c < 0 || c >= n) return fail(CB_EINVAL, "%s: family %d move %d: c = %d (0 <= index < %d)", who, f, m, c, n);
-      if (s < 0 || s >= n) return fail(CB_EINVAL, "%s: family %d move %d: s = %d (0 <= index < %d)", who, f, m, s, n);
-      if (v == F.root) return fail(CB_EINVAL, "%s: family %d move %d: v = %d is the root", who, f, m, v);
-      if (F.child_ptr[v] == F.child_ptr[v + 1]) return fail(CB_EINVAL, "%s: family %d move %d: v = %d is a leaf", who, f, m, v);
-      if (par[c] != v) return fail(CB_EINVAL, "%s: family %d move %d: c = %d is not a child of v = %d", who, f, m, c, v);
-      if (s == v) return fail(CB_EINVAL, "%s: family %d move %d: s = %d equals v", who, f, m, s);
-      if (par[s] != par[v])
-        return fail(CB_EINVAL, "%s: family %d move %d: s = %d is not a child of parent[v] = %d", who, f, m, s, par[v]);
-    }
+    const int rc_f = bl_check_moves(who, H, f, n_moves[f], moves + 3 * off_m[f]);
+    if (rc_f != CB_OK) return rc_f;
     if (n_moves[f] == 0) continue;
     const size_t n_blocks = ((size_t)F.n_units + 64 / S - 1) / (64 / S);
     const size_t fit = std::min(bound / ((size_t)F.n_units * sizeof(double)), (size_t)INT32_MAX / n_blocks);
@@ -305,6 +315,161 @@ extern "C" int cb_bl_nni_scan(cb_bl_s *h, const int *n_moves, const int *moves, 
         }
       }
       HIP_TRY(hipMemcpy(delta + off_m[f], ddelta, (size_t)n_moves[f] * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    // dll of the scanned families now holds l_u at the current indices -- the bits cb_bl_get's inside pass would write
+    std::vector<char> stale(n_fam);
+    for (int f = 0; f < n_fam; ++f) stale[f] = n_moves[f] > 0 && !h->ll_fresh[f];
+    rc = bl_read_ll(h, stale, nullptr);
+    if (rc != CB_OK) return rc;
+    for (int f = 0; f < n_fam; ++f)
+      if (stale[f]) h->ll_fresh[f] = 1;
+  }
+  if (fam_ll)
+    for (int f = 0; f < n_fam; ++f) fam_ll[f] = h->ll_fresh[f] ? h->fam_ll[f] : std::nan("");
+  return CB_OK;
+}
+
+constexpr size_t SUP_BYTES = (size_t)256 << 20;   // ll'[move][unit] and C[move][replicate] of one chunk of whole groups, at most (one
+                                                  // group always goes); the test hook CB_SUP_BYTES: the results do not depend on it
+constexpr int SUP_MAX_REP = 65536;
+
+extern "C" int cb_bl_supports(cb_bl_s *h, int n_rep, const uint64_t *seeds, const int *n_moves, const int *moves, double *alrt,
+                              int *sh_count, int *rell_count, double *delta_rep, double *fam_ll, double *kernel_ms) {
+  static const char *who = "cb_bl_supports";
+  if (!h) return fail(CB_EINVAL, "%s: NULL handle", who);
+  if (!n_moves || !seeds) return fail(CB_EINVAL, "%s: NULL argument", who);
+  if (n_rep < 1 || n_rep > SUP_MAX_REP) return fail(CB_EINVAL, "%s: n_rep = %d (1 <= replicates <= %d)", who, n_rep, SUP_MAX_REP);
+  // every triple and the grouping, on the host, before any device work
+  const EmForestHost &H = h->forest.host;
+  const int n_fam = H.n_fam(), S = h->forest.S;
+  std::vector<size_t> off_m(n_fam + 1, 0), off_g(n_fam + 1, 0);
+  for (int f = 0; f < n_fam; ++f) {
+    if (n_moves[f] < 0) return fail(CB_EINVAL, "%s: family %d: n_moves = %d", who, f, n_moves[f]);
+    off_m[f + 1] = off_m[f] + n_moves[f];
+  }
+  if (off_m[n_fam] > 0 && !moves) return fail(CB_EINVAL, "%s: NULL argument", who);
+  std::vector<int> group_ptr;                    // per family its groups' first moves and the end, within the family
+  std::vector<size_t> off_gp(n_fam + 1, 0);      // ... where they start in group_ptr
+  std::vector<std::vector<int>> cuts(n_fam);     // per family the groups at which its chunks start, and the end
+  const size_t bound = cb_hook_bytes("CB_SUP_BYTES", SUP_BYTES);
+  const size_t rep_tiles = ((size_t)n_rep + 63) / 64;
+  size_t max_moves = 0, max_chunk = 0, max_out = 0, max_groups = 0, max_units = 0;
+  for (int f = 0; f < n_fam; ++f) {
+    const EmFamHost &F = H.fam[f];
+    const int *mv = moves + 3 * off_m[f];
+    const int rc_f = bl_check_moves(who, H, f, n_moves[f], mv);
+    if (rc_f != CB_OK) return rc_f;
+    std::vector<char> seen(F.n_nodes, 0);
+    for (int m = 0; m < n_moves[f]; ++m) {
+      const int v = mv[3 * (size_t)m];
+      if (m > 0 && v == mv[3 * (size_t)(m - 1)]) continue;
+      if (seen[v])
+        return fail(CB_EINVAL, "%s: family %d move %d: v = %d comes back after another edge's moves (the moves of an edge must be "
+                    "consecutive)", who, f, m, v);
+      seen[v] = 1;
+      group_ptr.push_back(m);
+    }
+    group_ptr.push_back(n_moves[f]);
+    off_gp[f + 1] = group_ptr.size();
+    const size_t n_groups = off_gp[f + 1] - off_gp[f] - 1;
+    off_g[f + 1] = off_g[f] + n_groups;
+    if (n_moves[f] == 0) continue;
+    // chunks of whole groups: the byte bound, and the tiles of the scan's and the product's launches below 2^31
+    const int *gp = group_ptr.data() + off_gp[f];
+    const size_t n_blocks = ((size_t)F.n_units + 64 / S - 1) / (64 / S);
+    const size_t fit = std::min({bound / (((size_t)F.n_units + n_rep) * sizeof(double)), (size_t)INT32_MAX / n_blocks,
+                                 16 * ((size_t)INT32_MAX / rep_tiles - 1)});
+    for (size_t g = 0; g < n_groups;) {
+      cuts[f].push_back((int)g);
+      size_t e = g + 1;
+      while (e < n_groups && (size_t)(gp[e + 1] - gp[g]) <= fit) ++e;
+      const size_t nm = gp[e] - gp[g];
+      if (nm * n_blocks > (size_t)INT32_MAX || (nm + 15) / 16 * rep_tiles > (size_t)INT32_MAX)
+        return fail(CB_EINVAL, "%s: family %d: the %zu moves of the edge above v = %d need more than 2^31 - 1 tiles in one launch",
+                    who, f, nm, mv[3 * (size_t)gp[g]]);
+      max_chunk = std::max(max_chunk, nm);
+      max_out = std::max(max_out, nm * F.n_units);
+      g = e;
+    }
+    cuts[f].push_back((int)n_groups);
+    max_moves = std::max(max_moves, (size_t)n_moves[f]);
+    max_groups = std::max(max_groups, n_groups);
+    max_units = std::max(max_units, (size_t)F.n_units);
+  }
+  if (off_g[n_fam] > 0 && (!alrt || !sh_count || !rell_count)) return fail(CB_EINVAL, "%s: NULL argument", who);
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0.0;
+  if (max_moves > 0) {
+    HIP_TRY(hipSetDevice(h->forest.device));
+    // the messages of the families that are scanned, at the current indices: after a round the resident ones are its start's
+    CbKernelTimer passes(kernel_ms != nullptr, h->ev[0], h->ev[1]);
+    int rc = passes.begin(false);
+    if (rc != CB_OK) return rc;
+    for (int f = 0; f < n_fam; ++f)
+      if (n_moves[f] > 0) bl_launch_passes(h, f, true);
+    HIP_TRY(hipGetLastError());
+    if ((rc = passes.end(kernel_ms)) != CB_OK) return rc;
+    std::vector<int> inv(max_units);
+    CbDevBufs bufs;   // this call's: freed on every return path
+    int *dmoves = bufs.up<int>(nullptr, 3 * max_moves, rc), *dgp = bufs.up<int>(nullptr, max_groups + 1, rc);
+    int *dinv = bufs.up<int>(nullptr, max_units, rc);
+    double *dout = bufs.up<double>(nullptr, max_out, rc), *ddelta = bufs.up<double>(nullptr, max_moves, rc);
+    double *dW = bufs.up<double>(nullptr, (size_t)n_rep * max_units, rc), *dC = bufs.up<double>(nullptr, max_chunk * n_rep, rc);
+    double *dalrt = bufs.up<double>(nullptr, max_groups, rc);
+    int *dsh = bufs.up<int>(nullptr, max_groups, rc), *drell = bufs.up<int>(nullptr, max_groups, rc);
+    if (rc != CB_OK) return rc;
+    for (int f = 0; f < n_fam; ++f) {
+      if (n_moves[f] == 0) continue;
+      const EmFamView w = h->forest.view(f);
+      const EmFamHost &F = w.F;
+      const int U = F.n_units, *gp = group_ptr.data() + off_gp[f];
+      const size_t n_groups = off_g[f + 1] - off_g[f];
+      for (int k = 0; k < U; ++k) inv[F.perm[k]] = k;
+      HIP_TRY(hipMemcpy(dmoves, moves + 3 * off_m[f], 3 * (size_t)n_moves[f] * sizeof(int), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(dgp, gp, (n_groups + 1) * sizeof(int), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(dinv, inv.data(), (size_t)U * sizeof(int), hipMemcpyHostToDevice));
+      // the multiplicities of every replicate, once per family: every edge resamples the same sites
+      SupWeightArgs wa{};
+      wa.n_units = U; wa.k0 = (uint32_t)(seeds[f] & 0xFFFFFFFFu); wa.k1 = (uint32_t)(seeds[f] >> 32); wa.inv = dinv; wa.W = dW;
+      {
+        CbKernelTimer draw(kernel_ms != nullptr, h->ev[0], h->ev[1]);
+        double ms = 0.0;
+        if ((rc = draw.begin(false)) != CB_OK) return rc;
+        hipLaunchKernelGGL(sup_weights_kernel, dim3((unsigned)n_rep), dim3(256), 0, 0, wa);
+        HIP_TRY(hipGetLastError());
+        if ((rc = draw.end(&ms)) != CB_OK) return rc;
+        if (kernel_ms) kernel_ms[2] += ms;
+      }
+      NniArgs a{};
+      a.S = S; a.n_units = U; a.n_cats = F.n_cats; a.root = F.root; a.n_blocks = w.n_blocks;
+      a.parent = w.parent; a.child_ptr = w.child_ptr; a.child_idx = w.child_idx; a.qb = w.qb; a.unit_cat = w.unit_cat; a.P = h->dP;
+      a.pi_root = h->dpi; a.msg = w.msg; a.U = w.U; a.ll = w.ll; a.out = dout;
+      for (size_t ci = 0; ci + 1 < cuts[f].size(); ++ci) {
+        const int g0 = cuts[f][ci], g1 = cuts[f][ci + 1], m0 = gp[g0], nm = gp[g1] - m0;
+        a.moves = dmoves + 3 * (size_t)m0;
+        a.delta = ddelta + m0;
+        SupGemmArgs ga{};
+        ga.n_moves = nm; ga.n_rep = n_rep; ga.n_units = U; ga.out = dout; ga.ll = w.ll; ga.W = dW; ga.C = dC;
+        SupEdgeArgs ea{};
+        ea.n_rep = n_rep; ea.move0 = m0; ea.group_ptr = dgp + g0; ea.delta = a.delta; ea.C = dC;
+        ea.alrt = dalrt + g0; ea.sh_count = dsh + g0; ea.rell_count = drell + g0;
+        CbKernelTimer scan(kernel_ms != nullptr, h->ev[0], h->ev[2], h->ev[1]);
+        double ms[2] = {0.0, 0.0};
+        if ((rc = scan.begin(false)) != CB_OK) return rc;
+        hipLaunchKernelGGL(nni_scan_kernel, dim3((unsigned)nm * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
+        hipLaunchKernelGGL(nni_sum_kernel, dim3((unsigned)nm), dim3(64), 0, 0, a);
+        if ((rc = scan.lap()) != CB_OK) return rc;
+        hipLaunchKernelGGL(sup_gemm_kernel, dim3((unsigned)(((size_t)nm + 15) / 16 * rep_tiles)), dim3(256), 0, 0, ga, (int)rep_tiles);
+        hipLaunchKernelGGL(sup_edge_kernel, dim3((unsigned)(g1 - g0)), dim3(256), 0, 0, ea);
+        HIP_TRY(hipGetLastError());
+        if ((rc = scan.end(ms)) != CB_OK) return rc;
+        if (kernel_ms) kernel_ms[1] += ms[0], kernel_ms[2] += ms[1];
+        // (the next chunk writes the same buffers: stream order puts it behind this chunk's kernels and this copy)
+        if (delta_rep)
+          HIP_TRY(hipMemcpy(delta_rep + (off_m[f] + m0) * n_rep, dC, (size_t)nm * n_rep * sizeof(double), hipMemcpyDeviceToHost));
+      }
+      HIP_TRY(hipMemcpy(alrt + off_g[f], dalrt, n_groups * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(sh_count + off_g[f], dsh, n_groups * sizeof(int), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(rell_count + off_g[f], drell, n_groups * sizeof(int), hipMemcpyDeviceToHost));
     }
     // dll of the scanned families now holds l_u at the current indices -- the bits cb_bl_get's inside pass would write
     std::vector<char> stale(n_fam);

@@ -7,7 +7,9 @@ the stages `ml_branch_lengths` and `nj_ml_trees`) and the maximum-likelihood rat
 (`tree_site_rates`, the stages `ml_site_rates`, `ml_lengths_and_site_rates` and `nj_ml_rates_trees`); topology search by
 nearest-neighbour interchange scored on the GPU from the fitter's resident messages (`BranchLengthFitter.nni_scan`,
 `select_nni`, `apply_nni`, the stages `ml_nni_trees` and `nj_nni_trees`); marginal ancestral reconstruction from the same messages
-(`BranchLengthFitter.ancestral_states`, the stage `ml_ancestral_sequences`)."""
+(`BranchLengthFitter.ancestral_states`, the stage `ml_ancestral_sequences`); aLRT, SH-like and RELL supports of the internal edges
+by resampling the scan's per-site log-likelihoods on the GPU (`BranchLengthFitter.branch_supports`, the stage
+`ml_branch_supports`)."""
 from ._ble import (  # noqa: F401
     BleBank,
     branch_lengths,
@@ -32,3 +34,4 @@ from ._ml_lengths import BranchLengthFitter, ml_branch_lengths, nj_ml_trees  # n
 from ._site_rates import ml_lengths_and_site_rates, ml_site_rates, nj_ml_rates_trees, tree_site_rates  # noqa: F401,E402
 from ._nni import apply_nni, enumerate_nni_moves, ml_nni_trees, nj_nni_trees, select_nni  # noqa: F401,E402
 from ._ancestral import ml_ancestral_sequences  # noqa: F401,E402
+from ._supports import ml_branch_supports, read_supports, write_supports  # noqa: F401,E402

@@ -9,7 +9,8 @@ directories, `nj_ml_trees` the tree estimator `nj_trees` + `ml_branch_lengths`.
 
 The handle also scores the nearest-neighbour interchanges of its trees from the messages its passes leave resident (`nni_moves`,
 `nni_scan`; the search on top of them is `_nni.py`) and reconstructs the marginal posterior of the state at
-every node from the same messages (`ancestral_states`; the stage is `_ancestral.py`).
+every node from the same messages (`ancestral_states`; the stage is `_ancestral.py`), and resamples the
+scan's per-site log-likelihoods into local branch supports (`branch_supports`; the stage is `_supports.py`).
 
 Out of scope: changing a handle's topology in place, a continuous (off-grid) optimiser, S > 32."""
 import ctypes
@@ -58,6 +59,7 @@ class BranchLengthFitter(_lib.ResidentHandle):
         self._parent = np.split(self._args[0], np.cumsum(self.n_nodes)[:-1])
         self.last_nni_kernel_ms = (0.0, 0.0)   # (passes, scan) of the last nni_scan
         self.last_ancestral_kernel_ms = (0.0, 0.0)   # (passes, reconstruction) of the last ancestral_states
+        self.last_support_kernel_ms = (0.0, 0.0, 0.0)   # (passes, scan, resampling) of the last branch_supports
         self._create()
 
     def _create(self) -> None:
@@ -135,6 +137,53 @@ class BranchLengthFitter(_lib.ResidentHandle):
             return moves, deltas
         lls = [x.reshape(int(k), int(u)) for x, k, u in zip(np.split(ll, np.cumsum(sizes)[:-1]), n_moves, self.n_units)]
         return moves, deltas, lls
+
+    def branch_supports(self, num_replicates: int = 1000, seeds: Optional[Sequence[int]] = None, per_replicate: bool = False,
+                        moves: Optional[Sequence] = None):
+        """Local supports of the edge above every internal non-root node at the current indices (`cb_bl_supports`: the NNI scan,
+        then a resampling of its per-site log-likelihoods on the GPU) -> per family
+        (nodes, alrt, sh, rell) and with `per_replicate` also delta_rep: nodes int32 [g] the v of each group of `nni_moves()` in
+        its order, alrt float64 [g] = -2 max of the group's `nni_scan` deltas (negative where a neighbour beats the tree), sh and
+        rell float64 [g] the SH-like and RELL supports, counts over `num_replicates` (1 .. 65536) site resamples divided by it,
+        and delta_rep float64 [n_moves, num_replicates] the resampled deltas.  `seeds`: one 64-bit seed per family (default 0);
+        replicate r of a family depends on its seed and r alone.  A family with no move gets empty arrays; an edge none of whose
+        neighbours has a finite likelihood gets NaN three times.  `moves`: per family its own [n, 3] list in place of
+        `nni_moves()`, equal v consecutive (a subset of the edges, or of an edge's neighbours).  Changes nothing
+        `round()`, `indices()`, `log_likelihoods()`, `nni_scan()` or `ancestral_states()` return.  Sets
+        `last_support_kernel_ms` = (passes, scan, resampling)."""
+        n_fam = self.n_nodes.size
+        num_replicates = int(num_replicates)
+        seeds = [0] * n_fam if seeds is None else [int(s) for s in seeds]
+        if len(seeds) != n_fam:
+            raise ValueError(f"branch_supports: {len(seeds)} seeds for {n_fam} families")
+        seed_arr = np.array([s & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=np.uint64)
+        moves = self.nni_moves() if moves is None else [np.ascontiguousarray(m, dtype=np.int32).reshape(-1, 3) for m in moves]
+        if len(moves) != n_fam:
+            raise ValueError(f"branch_supports: {len(moves)} move lists for {n_fam} families")
+        n_moves = np.array([len(m) for m in moves], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(moves).reshape(-1), dtype=np.int32)
+        # the groups: runs of equal v (the library refuses a v that comes back)
+        nodes = [m[np.r_[True, m[1:, 0] != m[:-1, 0]], 0].astype(np.int32) if len(m) else np.zeros(0, dtype=np.int32) for m in moves]
+        n_groups = np.array([len(v) for v in nodes], dtype=np.int64)
+        total = int(n_groups.sum())
+        alrt = np.empty(total)
+        sh, rell = np.empty(total, dtype=np.int32), np.empty(total, dtype=np.int32)
+        rep = np.empty(int(n_moves.sum()) * max(num_replicates, 0)) if per_replicate else None
+        ms = (ctypes.c_double * 3)(0.0, 0.0, 0.0)
+        rc = _lib.load().cb_bl_supports(self._handle(), num_replicates, seed_arr.ctypes.data, n_moves.ctypes.data, flat.ctypes.data,
+                                        alrt.ctypes.data, sh.ctypes.data, rell.ctypes.data, rep.ctypes.data if per_replicate else None,
+                                        None, ctypes.addressof(ms))
+        if rc == _lib.CB_EINVAL:   # a refused call: the library's message names the value
+            raise _lib.CherryBankError(f"cb_bl_supports failed ({rc}): {_lib.load().cb_last_error().decode('utf-8', 'replace')}")
+        _lib.check(rc, "cb_bl_supports")
+        self.last_support_kernel_ms = (ms[0], ms[1], ms[2])
+        cuts = np.cumsum(n_groups)[:-1]
+        share = [[np.where(x >= 0, x / num_replicates, np.nan) for x in np.split(c, cuts)] for c in (sh, rell)]
+        out = [nodes, np.split(alrt, cuts), share[0], share[1]]
+        if per_replicate:
+            out.append([x.reshape(int(k), num_replicates)
+                        for x, k in zip(np.split(rep, np.cumsum(n_moves.astype(np.int64))[:-1] * num_replicates), n_moves)])
+        return [tuple(x[k] for x in out) for k in range(len(moves))]
 
     def ancestral_states(self, posteriors: bool = False):
         """The marginal posterior of the state at EVERY node (root, internal nodes, leaves) at the current indices

@@ -99,7 +99,8 @@ def select_nni(moves, delta, parent, min_gain: float = 0.0) -> np.ndarray:
 def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: List[str], rate_matrix_path: str,
                  num_nni_rounds: int = 10, num_rounds: int = 10, quantization_grid_center: float = 0.03,
                  quantization_grid_step: float = 1.1, quantization_grid_num_steps: int = 64, output_tree_dir: Optional[str] = None,
-                 output_likelihood_dir: Optional[str] = None, max_bank_bytes: int = DEFAULT_MAX_BANK_BYTES, _version="1") -> None:
+                 output_likelihood_dir: Optional[str] = None, max_bank_bytes: int = DEFAULT_MAX_BANK_BYTES,
+                 output_support_dir: Optional[str] = None, num_support_replicates: int = 1000, _version="1") -> None:
     """Improve the topologies of `<tree_dir>/<family>.txt` by likelihood: at most `num_nni_rounds` times, per family, fit the
     lengths of the current tree (`BranchLengthFitter`, at most `num_rounds` EM rounds), score ALL its nearest-neighbour
     interchanges (`nni_scan`), select those of positive gain at disjoint places (`select_nni`) and apply them (`apply_nni`).
@@ -111,12 +112,17 @@ def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: Lis
     Per family: `<output_tree_dir>/<family>.txt` (the input's node names and their order, every length a grid point),
     `<family>.nni` (per NNI round `<round> <log-likelihood before> <moves scanned> <selected> <applied> <log-likelihood after,
     same lengths>`, then `final <log-likelihood of the written tree>`: no number is below the one before it),
-    `<family>.profiling`, and `<output_likelihood_dir>/<family>.txt` as `ml_branch_lengths` writes it."""
+    `<family>.profiling`, and `<output_likelihood_dir>/<family>.txt` as `ml_branch_lengths` writes it.  With
+    `output_support_dir`, also `<output_support_dir>/<family>.txt` as `ml_branch_supports` writes it: the aLRT, SH-like and RELL
+    supports of the FINAL tree's internal edges from `num_support_replicates` site resamples (seed
+    `simulation.family_seed(family, 0)`), computed on the last handle that holds the final tree at its final lengths; without
+    it (the default) nothing else is written or computed."""
     from ..counting._host import read_msa, read_site_rates
     from ..counting._stage import _device_index
     from ..evaluation._likelihood import (_family_units, _stationary_distribution, dp_likelihood_computation_batch,
                                           write_log_likelihood)
     from ..io import read_rate_matrix
+    from ._supports import support_seeds, supports_of_trees, write_supports
     if output_tree_dir is None or output_likelihood_dir is None:
         raise ValueError("output_tree_dir and output_likelihood_dir are required")
     if _lib.load().cb_device_count() <= 0:
@@ -143,6 +149,7 @@ def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: Lis
     prof = [dict(create_time=0.0, scan_time=0.0, scan_kernel_ms=0.0, fit_time=0.0, handles=0, nni_rounds=0, moves_applied=0)
             for _ in families]
     final_ll: List[Optional[float]] = [None] * F
+    supports: List[Optional[tuple]] = [None] * F   # (with output_support_dir) the final trees' supports
     bank_bytes = [2 * grid.size * np.unique(r).size * Q.size * 8 for r in rates]
     # Per family: rnd = its NNI round; trees[f] = the tree the next handle takes -- the input, or a candidate (fitted[f] with the
     # moves sel[f] applied) that has to beat before[f].  ONE handle per pass over the work list: on a candidate its
@@ -187,6 +194,17 @@ def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: Lis
                 if any(want):
                     moves, delta = fit.nni_scan([m if w else m[:0] for m, w in zip(fit.nni_moves(), want)])
                 t_scan, ms_scan = time.time() - st_scan, fit.last_nni_kernel_ms[1]
+                picked = [moves[k][select_nni(moves[k], delta[k], _parent_array(trees[f]))] if want[k] else None
+                          for k, f in enumerate(fams)]
+                if output_support_dir is not None:
+                    # the families that end on this handle's tree at these lengths: no further round, or no move that gains
+                    ends = [bool(go[k]) and (not want[k] or len(picked[k]) == 0) for k in range(len(fams))]
+                    if any(ends):
+                        sup = fit.branch_supports(num_support_replicates, seeds=support_seeds([families[f] for f in fams], 0),
+                                                  moves=[m if e else m[:0] for m, e in zip(fit.nni_moves(), ends)])
+                        for k, f in enumerate(fams):
+                            if ends[k]:
+                                supports[f] = sup[k]
             for k, f in enumerate(fams):
                 for key, x in (("create_time", t_create), ("scan_time", t_scan), ("scan_kernel_ms", ms_scan),
                                ("fit_time", time.time() - st)):
@@ -209,7 +227,7 @@ def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: Lis
                     final_ll[f] = ll
                     continue
                 prof[f]["nni_rounds"] += 1
-                s = moves[k][select_nni(moves[k], delta[k], _parent_array(t))]
+                s = picked[k]
                 scanned[f], selected[f] = len(moves[k]), len(s)
                 if len(s) == 0:                                # no move gains: finished
                     logs[f].append(f"{rnd[f]} {ll!r} {scanned[f]} 0 0 {ll!r}\n")
@@ -219,6 +237,18 @@ def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: Lis
                 trees[f] = apply_nni(t, s)
                 nxt.append(f)
         work = nxt
+    if output_support_dir is not None:
+        os.makedirs(output_support_dir, exist_ok=True)
+        # a family whose last candidate was refused ends on the tree of an earlier handle: one more handle for those
+        rest = [f for f in range(F) if supports[f] is None]
+        if rest:
+            got, _ = supports_of_trees([trees[f] for f in rest], [codes[f] for f in rest], [rates[f] for f in rest], grid, Q, pi_root,
+                                       support_seeds([families[f] for f in rest], 0), int(num_support_replicates), device,
+                                       max_bank_bytes)
+            for f, res in zip(rest, got):
+                supports[f] = res
+        for f, family in enumerate(families):
+            write_supports(os.path.join(output_support_dir, family + ".txt"), list(trees[f].nodes()), supports[f])
     st = time.time()
     lls = dp_likelihood_computation_batch(trees, msas, [None] * F, [[float(x) for x in r] for r in rates], alphabet, pi_root, Q,
                                           device=device)
@@ -237,12 +267,13 @@ def nj_nni_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, nu
                  num_processes: int = 1, num_rounds: int = 10, num_nni_rounds: int = 10, output_tree_dir: Optional[str] = None,
                  output_site_rates_dir: Optional[str] = None, output_likelihood_dir: Optional[str] = None, remake=False,
                  quantization_grid_center=0.03, quantization_grid_step=1.1, quantization_grid_num_steps=64, verbose=True,
-                 seed=1234) -> Dict[str, str]:
+                 seed=1234, output_support_dir: Optional[str] = None, num_support_replicates: int = 1000) -> Dict[str, str]:
     """`nj_trees`, then `ml_nni_trees` on its trees at its site rates and the same grid: `nj_ml_trees`' interface plus
     `num_nni_rounds`, and under `functools.partial` a `tree_estimator` of the end-to-end pipelines.  Returns the output
     directories: `output_tree_dir` / `output_likelihood_dir` hold the searched trees and their likelihoods,
     `output_site_rates_dir` is `nj_trees`' own.  Both stages are cached on their own.  With no cache directory the three output
-    directories are required and the neighbour-joining trees and likelihoods go to their `nj_trees` subdirectories."""
+    directories are required and the neighbour-joining trees and likelihoods go to their `nj_trees` subdirectories.  With
+    `output_support_dir` the supports of the final trees are written there (`ml_nni_trees`); the returned dict is the same."""
     from ..caching import get_cache_dir
     from ._nj import nj_trees
     if _lib.load().cb_device_count() <= 0:
@@ -259,9 +290,10 @@ def nj_nni_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, nu
                   max_iters=max_iters, num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, **grid_args, **nj_out)
     nj = nj if nj is not None else nj_out
     out = dict(output_tree_dir=output_tree_dir, output_likelihood_dir=output_likelihood_dir)
+    sup = dict(output_support_dir=output_support_dir, num_support_replicates=num_support_replicates)
     ml = ml_nni_trees(tree_dir=nj["output_tree_dir"], msa_dir=msa_dir, site_rates_dir=nj["output_site_rates_dir"],
                       families=families, rate_matrix_path=rate_matrix_path, num_nni_rounds=num_nni_rounds, num_rounds=num_rounds,
-                      **grid_args, **out)
+                      **grid_args, **out, **sup)
     ml = ml if ml is not None else out
     return dict(output_tree_dir=ml["output_tree_dir"], output_site_rates_dir=nj["output_site_rates_dir"],
                 output_likelihood_dir=ml["output_likelihood_dir"])

@@ -618,7 +618,30 @@ int cb_em_destroy(cb_em h);
  *   [2]: the device time of the passes and of the reconstruction.  CB_EINVAL for a NULL handle or a NULL state.
  *   The call changes nothing cb_bl_round, cb_bl_get or cb_bl_nni_scan return.  Its device buffers are its own, freed before it
  *   returns; with post a family's nodes go in chunks that keep the device copy of post under 256 MiB (one node always goes);
- *   a node's results do not depend on the chunking or on the other nodes or families of the call. */
+ *   a node's results do not depend on the chunking or on the other nodes or families of the call.
+ *
+ * cb_bl_supports: local supports of the edge above every internal non-root node, by resampling the per-site log-likelihoods of
+ *   the edge's nearest-neighbour interchanges at the CURRENT indices.  n_moves / moves as for
+ *   cb_bl_nni_scan, validated in the same words; in addition a family's moves must be grouped by v -- equal v consecutive, no v
+ *   coming back later (CB_EINVAL names family and move) -- and the moves with one v are the group of the edge above v.  n_rep
+ *   replicates, 1 <= n_rep <= 65536 (CB_EINVAL names the value); seeds [n_fam] the families' 64-bit seeds.  With l_u the
+ *   family's per-site log-likelihood, ll'_m[u] the scan's and d_m[u] = ll'_m[u] - l_u (0 where l_u is not finite), replicate r
+ *   draws L = n_units sites with replacement: draw j takes word j & 3 of philox4x32_10(counter = (j >> 2, r, 0, 0x53555050),
+ *   key = (seed low word, seed high word)) and lands on site (word * L) >> 32 in the caller's order; w_r[u] counts the draws of
+ *   u and serves every edge of the family.  delta_m = sum_u d_m[u] is cb_bl_nni_scan's delta, delta_m^r = sum_u w_r[u] d_m[u].
+ *   Out, per group G (a move whose delta is not finite is left out; a group left empty gets NaN, -1, -1), the families' groups
+ *   concatenated in the order of their first moves:
+ *     alrt        -2 max_{m in G} delta_m  (negative where a neighbour beats the tree)
+ *     rell_count  the replicates with max_{m in G} delta_m^r <= 0
+ *     sh_count    the replicates with -max_{m in G} delta_m > t^r, t^r = the largest minus the second largest of {0} and the
+ *                 centred values delta_m^r - delta_m  (SH-like, centred at the exact expectation; 0 where alrt <= 0)
+ *   delta_rep (may be NULL) [sum n_moves][n_rep] the delta_m^r; fam_ll as cb_bl_nni_scan's; kernel_ms (may be NULL) [3]: the
+ *   device time of the passes, of the scan and of the resampling (weights, product, edge reduction).  The passes run first, as
+ *   in cb_bl_nni_scan.  Moves go in chunks of whole groups that keep ll' and delta_rep's device copy together under 256 MiB (one
+ *   group always goes) and every launch below 2^31 tiles (CB_EINVAL for a single group beyond that).  Fixed orders, no
+ *   floating-point atomics: a move's delta_m^r is bitwise independent of the other moves, replicates, chunks and families, and
+ *   the draws of replicate r do not depend on n_rep.  The call changes nothing cb_bl_round, cb_bl_get, cb_bl_nni_scan or
+ *   cb_bl_ancestral return; its device buffers are its own, freed before it returns. */
 #define CB_BL_MAX_CATS 64
 typedef struct cb_bl_s *cb_bl;
 int cb_bl_create(int device, int S, int T, const double *grid, const double *Q, const double *pi_root, int n_fam,
@@ -629,6 +652,8 @@ int cb_bl_get(cb_bl h, int *index, double *ll, double *fam_ll);
 int cb_bl_nni_scan(cb_bl h, const int *n_moves, const int *moves, double *delta, double *ll_moves, double *fam_ll,
                    double *kernel_ms);
 int cb_bl_ancestral(cb_bl h, int8_t *state, double *conf, double *post, double *fam_ll, double *kernel_ms);
+int cb_bl_supports(cb_bl h, int n_rep, const uint64_t *seeds, const int *n_moves, const int *moves, double *alrt, int *sh_count,
+                   int *rell_count, double *delta_rep, double *fam_ll, double *kernel_ms);
 int cb_bl_destroy(cb_bl h);
 
 /* ---- the maximum-likelihood rate category of every site on fixed full trees (S <= 32) ----------------------------------------
