@@ -12,6 +12,7 @@ from .phylogeny_estimation import ml_lengths_and_site_rates, ml_site_rates, nj_m
 from .phylogeny_estimation import apply_nni, ml_nni_trees, nj_nni_trees, select_nni  # noqa: F401,E402
 from .phylogeny_estimation import ml_ancestral_sequences  # noqa: F401,E402
 from .phylogeny_estimation import ml_branch_supports  # noqa: F401,E402
+from .phylogeny_estimation import neighbor_joining_device, neighbor_joining_device_batch  # noqa: F401,E402
 from ._cherryml_public_api import cherryml_public_api  # noqa: F401,E402
 from .simulation import simulate_msas  # noqa: F401,E402
 from .estimation import (EStep, RateMatrix, RateMatrixLearner, em_lg, jtt_ipw, quantized_transitions_mle,  # noqa: F401
@@ -28,4 +29,5 @@ __all__ = [
     "BranchLengthFitter", "ml_branch_lengths", "nj_ml_trees",
     "tree_site_rates", "ml_site_rates", "ml_lengths_and_site_rates", "nj_ml_rates_trees",
     "apply_nni", "select_nni", "ml_nni_trees", "nj_nni_trees", "ml_ancestral_sequences", "ml_branch_supports",
+    "neighbor_joining_device", "neighbor_joining_device_batch",
 ]

@@ -66,6 +66,7 @@ SIGNATURES = {
     "cb_ble_bank_destroy": (C.c_int, [_vp]),
     "cb_site_rate_gather": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "cb_ble_pairwise": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "cb_nj_batch": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cb_tree_likelihood": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp,
                                      C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "cb_tree_likelihood_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp,

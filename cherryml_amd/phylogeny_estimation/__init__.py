@@ -2,7 +2,8 @@
 two bisection passes, their coordinate ascent) and, around it, the reference's seeded divide-and-conquer
 cherry pairing (host) and tree / site-rate files (`fast_cherries`, `fast_cherries_family`).  Full trees: the same bisection
 for all pairs of sequences on the GPU (`pairwise_branch_lengths`) and neighbour joining on the host (`neighbor_joining`,
-`nj_tree_family`, the stage `nj_trees`); maximum-likelihood lengths on a fixed tree by EM on the GPU (`BranchLengthFitter`,
+`nj_tree_family`, the stage `nj_trees`) or, with `joiner="device"`, on the GPU (`neighbor_joining_device`,
+`neighbor_joining_device_batch`); maximum-likelihood lengths on a fixed tree by EM on the GPU (`BranchLengthFitter`,
 the stages `ml_branch_lengths` and `nj_ml_trees`) and the maximum-likelihood rate category of every site on it
 (`tree_site_rates`, the stages `ml_site_rates`, `ml_lengths_and_site_rates` and `nj_ml_rates_trees`); topology search by
 nearest-neighbour interchange scored on the GPU from the fitter's resident messages (`BranchLengthFitter.nni_scan`,
@@ -30,6 +31,7 @@ from ._fast_cherries import (  # noqa: F401,E402
     rate_categories_ble,
 )
 from ._nj import neighbor_joining, nj_distance_indices, nj_tree_family, nj_trees  # noqa: F401,E402
+from ._nj import neighbor_joining_device, neighbor_joining_device_batch, nj_join_records  # noqa: F401,E402
 from ._ml_lengths import BranchLengthFitter, ml_branch_lengths, nj_ml_trees  # noqa: F401,E402
 from ._site_rates import ml_lengths_and_site_rates, ml_site_rates, nj_ml_rates_trees, tree_site_rates  # noqa: F401,E402
 from ._nni import apply_nni, enumerate_nni_moves, ml_nni_trees, nj_nni_trees, select_nni  # noqa: F401,E402

@@ -313,8 +313,8 @@ def nj_ml_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, num
                 num_processes: int = 1, num_rounds: int = 10, output_tree_dir: Optional[str] = None,
                 output_site_rates_dir: Optional[str] = None, output_likelihood_dir: Optional[str] = None, remake=False,
                 quantization_grid_center=0.03, quantization_grid_step=1.1, quantization_grid_num_steps=64, verbose=True,
-                seed=1234) -> Dict[str, str]:
-    """`nj_trees`, then `ml_branch_lengths` on its trees at its site rates and the same grid: `nj_trees`' interface plus
+                seed=1234, joiner="host") -> Dict[str, str]:
+    """`nj_trees` (with its `joiner`), then `ml_branch_lengths` on its trees at its site rates and the same grid: `nj_trees`' interface plus
     `num_rounds`, and under `functools.partial` a `tree_estimator` of the end-to-end pipelines.  Returns the output directories:
     `output_tree_dir` / `output_likelihood_dir` hold the refitted trees and their likelihoods, `output_site_rates_dir` is
     `nj_trees`' own.  Both stages are cached on their own; `nj_trees`, its files and its cache keys are what they are without
@@ -331,7 +331,8 @@ def nj_ml_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, num
     grid_args = dict(quantization_grid_center=quantization_grid_center, quantization_grid_step=quantization_grid_step,
                      quantization_grid_num_steps=quantization_grid_num_steps)
     nj = nj_trees(msa_dir=msa_dir, families=families, rate_matrix_path=rate_matrix_path, num_rate_categories=num_rate_categories,
-                  max_iters=max_iters, num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, **grid_args, **nj_out)
+                  max_iters=max_iters, num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, joiner=joiner, **grid_args,
+                  **nj_out)
     nj = nj if nj is not None else nj_out
     ml_out = dict(output_tree_dir=output_tree_dir, output_likelihood_dir=output_likelihood_dir)
     ml = ml_branch_lengths(tree_dir=nj["output_tree_dir"], msa_dir=msa_dir, site_rates_dir=nj["output_site_rates_dir"],

@@ -267,9 +267,10 @@ def nj_nni_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, nu
                  num_processes: int = 1, num_rounds: int = 10, num_nni_rounds: int = 10, output_tree_dir: Optional[str] = None,
                  output_site_rates_dir: Optional[str] = None, output_likelihood_dir: Optional[str] = None, remake=False,
                  quantization_grid_center=0.03, quantization_grid_step=1.1, quantization_grid_num_steps=64, verbose=True,
-                 seed=1234, output_support_dir: Optional[str] = None, num_support_replicates: int = 1000) -> Dict[str, str]:
-    """`nj_trees`, then `ml_nni_trees` on its trees at its site rates and the same grid: `nj_ml_trees`' interface plus
-    `num_nni_rounds`, and under `functools.partial` a `tree_estimator` of the end-to-end pipelines.  Returns the output
+                 seed=1234, output_support_dir: Optional[str] = None, num_support_replicates: int = 1000,
+                 joiner="host") -> Dict[str, str]:
+    """`nj_trees` (with its `joiner`), then `ml_nni_trees` on its trees at its site rates and the same grid: `nj_ml_trees`'
+    interface plus `num_nni_rounds`, and under `functools.partial` a `tree_estimator` of the end-to-end pipelines.  Returns the output
     directories: `output_tree_dir` / `output_likelihood_dir` hold the searched trees and their likelihoods,
     `output_site_rates_dir` is `nj_trees`' own.  Both stages are cached on their own.  With no cache directory the three output
     directories are required and the neighbour-joining trees and likelihoods go to their `nj_trees` subdirectories.  With
@@ -287,7 +288,8 @@ def nj_nni_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, nu
     grid_args = dict(quantization_grid_center=quantization_grid_center, quantization_grid_step=quantization_grid_step,
                      quantization_grid_num_steps=quantization_grid_num_steps)
     nj = nj_trees(msa_dir=msa_dir, families=families, rate_matrix_path=rate_matrix_path, num_rate_categories=num_rate_categories,
-                  max_iters=max_iters, num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, **grid_args, **nj_out)
+                  max_iters=max_iters, num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, joiner=joiner, **grid_args,
+                  **nj_out)
     nj = nj if nj is not None else nj_out
     out = dict(output_tree_dir=output_tree_dir, output_likelihood_dir=output_likelihood_dir)
     sup = dict(output_support_dir=output_support_dir, num_support_replicates=num_support_replicates)

@@ -288,11 +288,13 @@ def nj_ml_rates_trees(*, msa_dir: str, families: List[str], rate_matrix_path: st
                       num_processes: int = 1, num_rounds: int = 10, num_outer_iterations: int = 3,
                       output_tree_dir: Optional[str] = None, output_site_rates_dir: Optional[str] = None,
                       output_likelihood_dir: Optional[str] = None, remake=False, quantization_grid_center=0.03,
-                      quantization_grid_step=1.1, quantization_grid_num_steps=64, verbose=True, seed=1234) -> Dict[str, str]:
+                      quantization_grid_step=1.1, quantization_grid_num_steps=64, verbose=True, seed=1234,
+                      joiner="host") -> Dict[str, str]:
     """`nj_trees`, then `ml_lengths_and_site_rates` on its trees and site rates and the same grid: `nj_ml_trees`' interface plus
     `num_outer_iterations`, and under `functools.partial` a `tree_estimator` of the end-to-end pipelines.  Returns the three output
     directories of the refit -- the site-rate directory is the refitted one.  Both stages are cached on their own.  With no cache
-    directory the three output directories are required and `nj_trees`' own files go to their `nj_trees` subdirectories."""
+    directory the three output directories are required and `nj_trees`' own files go to their `nj_trees` subdirectories.
+    `joiner` is `nj_trees`'."""
     from ..caching import get_cache_dir
     from ._nj import nj_trees
     nj_out = dict(output_tree_dir=None, output_site_rates_dir=None, output_likelihood_dir=None)
@@ -304,7 +306,8 @@ def nj_ml_rates_trees(*, msa_dir: str, families: List[str], rate_matrix_path: st
     grid_args = dict(quantization_grid_center=quantization_grid_center, quantization_grid_step=quantization_grid_step,
                      quantization_grid_num_steps=quantization_grid_num_steps)
     nj = nj_trees(msa_dir=msa_dir, families=families, rate_matrix_path=rate_matrix_path, num_rate_categories=num_rate_categories,
-                  max_iters=max_iters, num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, **grid_args, **nj_out)
+                  max_iters=max_iters, num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, joiner=joiner, **grid_args,
+                  **nj_out)
     nj = nj if nj is not None else nj_out
     ml = ml_lengths_and_site_rates(tree_dir=nj["output_tree_dir"], msa_dir=msa_dir, site_rates_dir=nj["output_site_rates_dir"],
                                    families=families, rate_matrix_path=rate_matrix_path, num_rate_categories=num_rate_categories,

@@ -442,6 +442,24 @@ int cb_site_rate_gather(int device, int S, int R, int n, int L, const double *te
  * device visible: CB_EHIP.  kernel_ms (may be NULL): GPU time of the two kernels, inputs already resident, by HIP events. */
 int cb_ble_pairwise(int device, int S, int T, int R, const double *logP, const int8_t *seqs, int n, int L,
                     const int *site_to_rate, int *index, double *kernel_ms);
+/* Canonical neighbour joining (Saitou & Nei 1987, Studier & Keppler 1988) of n_fam families on the device: the join loop of
+ * phylogeny_estimation/_nj.py:neighbor_joining, operation for operation, so that only the order of the row sums can differ
+ * (one wave per row: lane l adds the columns l, l + 64, ... onto 0.0, then the xor butterfly over 32, 16, 8, 4, 2, 1).
+ * n [n_fam]: the leaves of every family; D: the symmetric float64 matrices D_f [n_f][n_f], row-major, concatenated.  Out:
+ *   join_nodes, join_len [sum_f max(n_f - 3, 0)][2], the families' join records concatenated: leaves are 0 .. n_f - 1, the node
+ *   join k makes is n_f + k; column 0 is the member with the lower place in the active list (leaves in the given order, joined
+ *   nodes behind them in join order); lengths are raw, not clamped.  While m > 3 nodes are active the pair minimising
+ *   (m - 2) d_ij - (r_i + r_j) is joined, on ties the first pair of the active list;
+ *   final_nodes [n_fam][3], final_D [n_fam][9]: the last three active nodes in active-list order and their distances (the root
+ *   step is the caller's); n_f = 3 or 2: the leaves themselves with their distances, unused slots -1 / 0;
+ *   kernel_ms (may be NULL): GPU time of the join launches, inputs already resident, by HIP events.
+ * Three launches per join serve all families of a chunk; the families go in chunks of whole families under 512 MiB of resident
+ * matrices (a family alone above that runs alone), and a family's results do not depend on batch, chunk or order.  Every
+ * argument is validated on the host before any device work (CB_EINVAL, naming family and value: NULL pointer, n_fam < 1,
+ * n_f < 2, an n_f whose matrix passes 2^31 - 1 entries, an entry negative or not finite, a non-zero diagonal entry,
+ * D[i][j] != D[j][i]); no device visible: CB_EHIP. */
+int cb_nj_batch(int device, int n_fam, const int *n, const double *D, int *join_nodes, double *join_len, int *final_nodes,
+                double *final_D, double *kernel_ms);
 
 /* ---- held-out log-likelihood of ONE family under one model (tail of SURVEY 8f #4) ---------------
  * Replaces the per-(node, site) python loops of cherryml/evaluation/_likelihood.py:47-327
