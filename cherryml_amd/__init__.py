@@ -13,6 +13,8 @@ from .phylogeny_estimation import apply_nni, ml_nni_trees, nj_nni_trees, select_
 from .phylogeny_estimation import ml_ancestral_sequences  # noqa: F401,E402
 from .phylogeny_estimation import ml_branch_supports  # noqa: F401,E402
 from .phylogeny_estimation import neighbor_joining_device, neighbor_joining_device_batch  # noqa: F401,E402
+from .phylogeny_estimation import (bootstrap_nj_records, bootstrap_supports, nj_bootstrap_supports,  # noqa: F401,E402
+                                   splits_of_join_records, tree_splits)
 from ._cherryml_public_api import cherryml_public_api  # noqa: F401,E402
 from .simulation import simulate_msas  # noqa: F401,E402
 from .estimation import (EStep, RateMatrix, RateMatrixLearner, em_lg, jtt_ipw, quantized_transitions_mle,  # noqa: F401
@@ -30,4 +32,5 @@ __all__ = [
     "tree_site_rates", "ml_site_rates", "ml_lengths_and_site_rates", "nj_ml_rates_trees",
     "apply_nni", "select_nni", "ml_nni_trees", "nj_nni_trees", "ml_ancestral_sequences", "ml_branch_supports",
     "neighbor_joining_device", "neighbor_joining_device_batch",
+    "bootstrap_nj_records", "bootstrap_supports", "nj_bootstrap_supports", "splits_of_join_records", "tree_splits",
 ]

@@ -3,10 +3,10 @@
 // host enqueues three launches per join of its largest family without waiting in between.
 #include "cb_internal.hip.h"
 #include "nj.hip.h"
+#include "nj_host.hip.h"
 
 namespace {
 constexpr size_t NJ_BYTES = (size_t)512 << 20;   // resident matrices of one chunk (test hook: CB_NJ_BYTES)
-constexpr int NJ_MAX_FAMILIES = 65535;           // of one chunk: the family is a grid dimension
 
 int nj_validate(int n_fam, const int *n, const double *D) {
   if (n_fam < 1) return fail(CB_EINVAL, "cb_nj_batch: n_fam = %d families (at least 1)", n_fam);
@@ -38,35 +38,35 @@ int nj_validate(int n_fam, const int *n, const double *D) {
   return CB_OK;
 }
 
-// the device buffers of the largest chunk, reused by every chunk
-struct NjBufs {
-  CbDevBufs d;
-  NjFamily *fams = nullptr;
-  double *D = nullptr, *r = nullptr, *tmp = nullptr, *join_len = nullptr, *final_D = nullptr;
-  int *rank = nullptr, *node = nullptr, *join_nodes = nullptr, *final_nodes = nullptr;
-  NjCand *cand = nullptr;
-  int alloc(size_t fam_cap, size_t mat_cap, size_t vec_cap, size_t join_cap) {
-    int rc = CB_OK;
-    fams = d.up<NjFamily>(nullptr, fam_cap, rc);
-    D = d.up<double>(nullptr, mat_cap, rc);
-    r = d.up<double>(nullptr, vec_cap, rc);
-    tmp = d.up<double>(nullptr, vec_cap, rc);
-    rank = d.up<int>(nullptr, vec_cap, rc);
-    node = d.up<int>(nullptr, vec_cap, rc);
-    cand = d.up<NjCand>(nullptr, vec_cap, rc);
-    join_nodes = d.up<int>(nullptr, join_cap * 2, rc);
-    join_len = d.up<double>(nullptr, join_cap * 2, rc);
-    final_nodes = d.up<int>(nullptr, fam_cap * 3, rc);
-    final_D = d.up<double>(nullptr, fam_cap * 9, rc);
-    return rc;
-  }
-};
-
-struct NjChunk {
-  int f0, f1;                      // families [f0, f1)
-  size_t mat, vec, joins;          // entries of its matrices, slots, join records
-};
 }  // namespace
+
+int cb_nj_join_chunk(const NjBufs &b, int nf_c, int n_max, size_t joins, bool timed, double *ms_total, int *join_nodes,
+                     double *join_len, int *final_nodes, double *final_D) {
+  int rc;
+  CbKernelTimer timer(timed);
+  if ((rc = timer.begin(false)) != CB_OK) return rc;
+  for (int t = 0; t < n_max - 3; ++t) {         // all iterations enqueued, no wait in between
+    const int m = n_max - t;
+    hipLaunchKernelGGL(nj_rowsum_kernel, dim3((unsigned)((m + NJ_WAVES - 1) / NJ_WAVES), (unsigned)nf_c), dim3(NJ_BLOCK), 0, 0, t,
+                       (const NjFamily *)b.fams, (const double *)b.D, b.r);
+    hipLaunchKernelGGL(nj_argmin_kernel, dim3((unsigned)nj_num_cands(m), (unsigned)nf_c), dim3(NJ_BLOCK), 0, 0, t,
+                       (const NjFamily *)b.fams, (const double *)b.D, (const double *)b.r, (const int *)b.rank, b.cand);
+    hipLaunchKernelGGL(nj_join_kernel, dim3((unsigned)nf_c), dim3(NJ_BLOCK), 0, 0, t, (const NjFamily *)b.fams, b.D,
+                       (const double *)b.r, b.tmp, b.rank, b.node, (const NjCand *)b.cand, b.join_nodes, b.join_len,
+                       b.final_nodes, b.final_D);
+  }
+  double ms = 0.0;
+  if ((rc = timer.end(&ms)) != CB_OK) return rc;
+  *ms_total += ms;
+  HIP_TRY(hipGetLastError());
+  if (joins) {
+    HIP_TRY(hipMemcpy(join_nodes, b.join_nodes, joins * 2 * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(join_len, b.join_len, joins * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  HIP_TRY(hipMemcpy(final_nodes, b.final_nodes, (size_t)nf_c * 3 * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(final_D, b.final_D, (size_t)nf_c * 9 * sizeof(double), hipMemcpyDeviceToHost));
+  return CB_OK;
+}
 
 extern "C" int cb_nj_batch(int device, int n_fam, const int *n, const double *D, int *join_nodes, double *join_len,
                            int *final_nodes, double *final_D, double *kernel_ms) {
@@ -116,30 +116,9 @@ extern "C" int cb_nj_batch(int device, int n_fam, const int *n, const double *D,
     HIP_TRY(hipMemcpyAsync(b.rank, iota.data(), c.vec * sizeof(int), hipMemcpyHostToDevice, 0));
     HIP_TRY(hipMemcpyAsync(b.node, iota.data(), c.vec * sizeof(int), hipMemcpyHostToDevice, 0));
     HIP_TRY(hipStreamSynchronize(0));           // (fams and iota are rewritten by the next chunk)
-    if (n_max > 3) {
-      CbKernelTimer timer(kernel_ms != nullptr);
-      if ((rc = timer.begin(false)) != CB_OK) return rc;
-      for (int t = 0; t < n_max - 3; ++t) {     // all iterations enqueued, no wait in between
-        const int m = n_max - t;
-        hipLaunchKernelGGL(nj_rowsum_kernel, dim3((unsigned)((m + NJ_WAVES - 1) / NJ_WAVES), (unsigned)nf_c), dim3(NJ_BLOCK), 0, 0, t,
-                           (const NjFamily *)b.fams, (const double *)b.D, b.r);
-        hipLaunchKernelGGL(nj_argmin_kernel, dim3((unsigned)nj_num_cands(m), (unsigned)nf_c), dim3(NJ_BLOCK), 0, 0, t,
-                           (const NjFamily *)b.fams, (const double *)b.D, (const double *)b.r, (const int *)b.rank, b.cand);
-        hipLaunchKernelGGL(nj_join_kernel, dim3((unsigned)nf_c), dim3(NJ_BLOCK), 0, 0, t, (const NjFamily *)b.fams, b.D,
-                           (const double *)b.r, b.tmp, b.rank, b.node, (const NjCand *)b.cand, b.join_nodes, b.join_len,
-                           b.final_nodes, b.final_D);
-      }
-      double ms = 0.0;
-      if ((rc = timer.end(&ms)) != CB_OK) return rc;
-      ms_total += ms;
-      HIP_TRY(hipGetLastError());
-      if (c.joins) {
-        HIP_TRY(hipMemcpy(join_nodes + join0 * 2, b.join_nodes, c.joins * 2 * sizeof(int), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(join_len + join0 * 2, b.join_len, c.joins * 2 * sizeof(double), hipMemcpyDeviceToHost));
-      }
-      HIP_TRY(hipMemcpy(final_nodes + (size_t)c.f0 * 3, b.final_nodes, (size_t)nf_c * 3 * sizeof(int), hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(final_D + (size_t)c.f0 * 9, b.final_D, (size_t)nf_c * 9 * sizeof(double), hipMemcpyDeviceToHost));
-    }
+    if (n_max > 3 && (rc = cb_nj_join_chunk(b, nf_c, n_max, c.joins, kernel_ms != nullptr, &ms_total, join_nodes + join0 * 2,
+                                            join_len + join0 * 2, final_nodes + (size_t)c.f0 * 3, final_D + (size_t)c.f0 * 9)) != CB_OK)
+      return rc;
     // three or two leaves are not joined: the leaves themselves with their distances, unused slots -1 / 0
     size_t at = mat0;
     for (int f = c.f0; f < c.f1; ++f) {

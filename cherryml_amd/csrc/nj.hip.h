@@ -13,22 +13,10 @@
 #include <climits>
 #include <cstddef>
 
+#include "nj_layout.h"                // NjFamily, NjCand
+
 #define NJ_BLOCK 256                  // threads of every workgroup: four waves
 #define NJ_WAVES (NJ_BLOCK / 64)
-
-// one family of a chunk: where its arrays start in the chunk's buffers
-struct NjFamily {
-  int n;            // leaves = slots = the row stride of D
-  int join0;        // its first join record in the chunk's join_nodes / join_len
-  size_t d0;        // its matrix in the chunk's D
-  size_t v0;        // its slot vectors (r, tmp, rank, node) and its candidates
-};
-
-// a candidate of the argmin: the criterion, the ranks (lower, higher) and the slots (of the lower rank, of the higher rank)
-struct NjCand {
-  double crit;
-  int ra, rb, sa, sb;
-};
 
 // the total order (crit, lower rank, higher rank): ranks are distinct, so no two pairs compare equal
 __device__ __forceinline__ bool nj_before(const NjCand &x, const NjCand &y) {

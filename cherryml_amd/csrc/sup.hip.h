@@ -23,26 +23,11 @@
 //                       and a popcount per wave, an integer sum over the waves in LDS.  delta is nni_sum_kernel's, as it is.
 #pragma once
 #include "common.hip.h"
+#include "philox.hip.h"   // sup_philox
 
 constexpr int SUP_WINDOW = 16384;        // sites per histogram window (64 KiB of LDS)
 constexpr int SUP_KT = 32;               // units per LDS slab of the product
 constexpr uint32_t SUP_TAG = 0x53555050u;   // the fourth counter word: this stream is nobody else's
-
-__device__ __forceinline__ void sup_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                           uint32_t x[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
-}
 
 struct SupWeightArgs {
   int n_units;              // L

@@ -10,7 +10,8 @@ nearest-neighbour interchange scored on the GPU from the fitter's resident messa
 `select_nni`, `apply_nni`, the stages `ml_nni_trees` and `nj_nni_trees`); marginal ancestral reconstruction from the same messages
 (`BranchLengthFitter.ancestral_states`, the stage `ml_ancestral_sequences`); aLRT, SH-like and RELL supports of the internal edges
 by resampling the scan's per-site log-likelihoods on the GPU (`BranchLengthFitter.branch_supports`, the stage
-`ml_branch_supports`)."""
+`ml_branch_supports`); Felsenstein's bootstrap of the neighbour-joining tree, the resampled distances as one matrix product per pair
+of sequences and the joins on the GPU (`bootstrap_nj_records`, `bootstrap_supports`, the stage `nj_bootstrap_supports`)."""
 from ._ble import (  # noqa: F401
     BleBank,
     branch_lengths,
@@ -37,3 +38,13 @@ from ._site_rates import ml_lengths_and_site_rates, ml_site_rates, nj_ml_rates_t
 from ._nni import apply_nni, enumerate_nni_moves, ml_nni_trees, nj_nni_trees, select_nni  # noqa: F401,E402
 from ._ancestral import ml_ancestral_sequences  # noqa: F401,E402
 from ._supports import ml_branch_supports, read_supports, write_supports  # noqa: F401,E402
+from ._bootstrap import (  # noqa: F401,E402
+    bootstrap_nj_records,
+    bootstrap_supports,
+    nj_bootstrap_supports,
+    read_bootstrap_supports,
+    splits_of_join_records,
+    supports_of_records,
+    tree_splits,
+    write_bootstrap_supports,
+)

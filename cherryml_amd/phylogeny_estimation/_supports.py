@@ -15,8 +15,8 @@ device; `ml_branch_supports` is the stage on tree / MSA / site-rate directories,
 supports of their final trees on request.  This is not FastTree's arithmetic (its SH-like test resamples the three topologies
 around an edge with its own constants), and the neighbours keep the tree's lengths: PhyML's aLRT re-optimises them.
 
-Out of scope: Felsenstein's bootstrap (rebuilding trees per replicate), re-optimising lengths per neighbour, supports under the
-400-state model or S > 32, writing supports into the tree file format."""
+Felsenstein's bootstrap (rebuilding trees per replicate) is `_bootstrap.py`.  Out of scope: re-optimising lengths per neighbour,
+supports under the 400-state model or S > 32, writing supports into the tree file format."""
 import os
 import time
 from typing import Dict, List, Optional, Sequence

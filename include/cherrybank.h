@@ -460,6 +460,33 @@ int cb_ble_pairwise(int device, int S, int T, int R, const double *logP, const i
  * D[i][j] != D[j][i]); no device visible: CB_EHIP. */
 int cb_nj_batch(int device, int n_fam, const int *n, const double *D, int *join_nodes, double *join_len, int *final_nodes,
                 double *final_D, double *kernel_ms);
+/* Felsenstein's bootstrap of one family on the device: n_rep resamples of the L sites (with replacement), per resample the
+ * all-pairs distances of cb_ble_pairwise at the resample's site multiplicities, and cb_nj_batch's joins of every resample's
+ * matrix D_b = grid[index_b] (0 on the diagonal), which never leaves the device.  logP [T][R][S][S], seqs [n][L], site_to_rate [L]
+ * as cb_ble_pairwise takes them; grid [T]: the branch lengths of the bank's grid points.  For a pair (i, j) the curve of replicate
+ * b is F[b][t] = sum_s w_b[s] (logP[t][rate(s)][x_s][y_s] + logP[t][rate(s)][y_s][x_s]) over the sites observed in both sequences,
+ * formed for all replicates at once as one float64 product on the matrix cores (k from site 0 upwards), and the reference's
+ * bisection (low = 0, high = T - 1, mid = low + (high - low) / 2, F[mid] > F[mid + 1] keeps the lower half) runs on it: a pair
+ * with no commonly observed site of positive weight gets T - 1.  A site keeps its rate category when it is drawn.
+ *   weights [n_rep][L] or NULL: the multiplicities w_b[s] as doubles.  NULL: drawn on the device -- draw j of replicate b takes
+ *   word j & 3 of Philox4x32-10 at counter (j >> 2, b, 0, 0x424F4F54) with key (seed low word, seed high word) and lands on site
+ *   (word * L) >> 32, L draws per replicate, sites in the caller's order; a replicate's weights depend on (seed, b, L) alone.
+ * Out:
+ *   join_nodes, join_len [n_rep max(n - 3, 0)][2], final_nodes [n_rep][3], final_D [n_rep][9]: as cb_nj_batch writes them for
+ *   n_rep "families" of n leaves each (n = 3 or 2: the leaves themselves with their distances, unused slots -1 / 0);
+ *   index [n_rep][n][n] (may be NULL): the grid indices, symmetric, -1 on the diagonal;
+ *   weights_out [n_rep][L] (may be NULL): the weights used;
+ *   kernel_ms [3] (may be NULL): GPU time of the weight draws, of the distance kernel and of the join launches, by HIP events.
+ * The replicates go in chunks of whole replicates under 512 MiB of resident matrices (a replicate alone above that runs alone);
+ * a replicate's results do not depend on n_rep or on the chunks.  Every argument is validated on the host before any device
+ * work (CB_EINVAL, naming the argument): what cb_ble_pairwise refuses, n_rep < 1, T above 1024, an n whose matrix passes
+ * 2^31 - 1 entries, a grid that is not finite, positive and increasing, a weight that is negative, not finite or not an integer
+ * value, and a bank entry that is not finite -- in the product a zero weight times -inf would be NaN and poison the curve of
+ * every replicate of the pair, where the gather of cb_ble_pairwise skips nothing either but never multiplies.  No device
+ * visible: CB_EHIP. */
+int cb_boot_nj(int device, int S, int T, int R, const double *logP, const double *grid, const int8_t *seqs, int n, int L,
+               const int *site_to_rate, int n_rep, uint64_t seed, const double *weights, int *join_nodes, double *join_len,
+               int *final_nodes, double *final_D, int *index, double *weights_out, double *kernel_ms);
 
 /* ---- held-out log-likelihood of ONE family under one model (tail of SURVEY 8f #4) ---------------
  * Replaces the per-(node, site) python loops of cherryml/evaluation/_likelihood.py:47-327
