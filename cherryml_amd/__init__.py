@@ -15,6 +15,8 @@ from .phylogeny_estimation import ml_branch_supports  # noqa: F401,E402
 from .phylogeny_estimation import neighbor_joining_device, neighbor_joining_device_batch  # noqa: F401,E402
 from .phylogeny_estimation import (bootstrap_nj_records, bootstrap_supports, nj_bootstrap_supports,  # noqa: F401,E402
                                    splits_of_join_records, tree_splits)
+from .phylogeny_estimation import (nj_transfer_supports, read_transfer_supports, transfer_bootstrap_supports,  # noqa: F401,E402
+                                   transfer_distances, transfer_supports_of_records, write_transfer_supports)
 from ._cherryml_public_api import cherryml_public_api  # noqa: F401,E402
 from .simulation import simulate_msas  # noqa: F401,E402
 from .estimation import (EStep, RateMatrix, RateMatrixLearner, em_lg, jtt_ipw, quantized_transitions_mle,  # noqa: F401
@@ -33,4 +35,6 @@ __all__ = [
     "apply_nni", "select_nni", "ml_nni_trees", "nj_nni_trees", "ml_ancestral_sequences", "ml_branch_supports",
     "neighbor_joining_device", "neighbor_joining_device_batch",
     "bootstrap_nj_records", "bootstrap_supports", "nj_bootstrap_supports", "splits_of_join_records", "tree_splits",
+    "transfer_distances", "transfer_supports_of_records", "transfer_bootstrap_supports", "nj_transfer_supports",
+    "read_transfer_supports", "write_transfer_supports",
 ]

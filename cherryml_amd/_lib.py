@@ -69,6 +69,7 @@ SIGNATURES = {
     "cb_nj_batch": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cb_boot_nj": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_uint64, _vp,
                              _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cb_transfer_support": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "cb_tree_likelihood": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp,
                                      C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "cb_tree_likelihood_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp,

@@ -11,7 +11,9 @@ nearest-neighbour interchange scored on the GPU from the fitter's resident messa
 (`BranchLengthFitter.ancestral_states`, the stage `ml_ancestral_sequences`); aLRT, SH-like and RELL supports of the internal edges
 by resampling the scan's per-site log-likelihoods on the GPU (`BranchLengthFitter.branch_supports`, the stage
 `ml_branch_supports`); Felsenstein's bootstrap of the neighbour-joining tree, the resampled distances as one matrix product per pair
-of sequences and the joins on the GPU (`bootstrap_nj_records`, `bootstrap_supports`, the stage `nj_bootstrap_supports`)."""
+of sequences and the joins on the GPU (`bootstrap_nj_records`, `bootstrap_supports`, the stage `nj_bootstrap_supports`); the transfer bootstrap of the same replicates, every split of the tree against every split of
+every replicate by xor and popcount on the GPU (`transfer_distances`, `transfer_bootstrap_supports`, the stage
+`nj_transfer_supports`)."""
 from ._ble import (  # noqa: F401
     BleBank,
     branch_lengths,
@@ -47,4 +49,12 @@ from ._bootstrap import (  # noqa: F401,E402
     supports_of_records,
     tree_splits,
     write_bootstrap_supports,
+)
+from ._transfer import (  # noqa: F401,E402
+    nj_transfer_supports,
+    read_transfer_supports,
+    transfer_bootstrap_supports,
+    transfer_distances,
+    transfer_supports_of_records,
+    write_transfer_supports,
 )

@@ -15,8 +15,11 @@ curves, the distance matrices are written where `cb_nj_batch`'s join kernels rea
 * `bootstrap_supports`: (nodes, support) for the edges above the internal non-root nodes of a given tree.
 * `nj_bootstrap_supports`: the stage on tree / MSA / site-rate directories.
 
+The transfer bootstrap of the same replicates, which judges a split by the closest split of a replicate's tree and not by an
+exact match, is `_transfer.py` (`nj_transfer_supports`).
+
 Out of scope: re-estimating the site rates per replicate (a site keeps its rate category when it is drawn), consensus trees,
-the transfer bootstrap, re-optimising lengths or topology by maximum likelihood per replicate."""
+re-optimising lengths or topology by maximum likelihood per replicate."""
 import ctypes
 import os
 import time
@@ -223,30 +226,13 @@ def read_bootstrap_supports(path: str) -> Dict[str, float]:
     return {x[0]: float(x[1]) for x in (ln.split() for ln in lines[1:] if ln)}
 
 
-@cached_computation(output_dirs=["output_support_dir"])
-def nj_bootstrap_supports(tree_dir: str, msa_dir: str, site_rates_dir: str, families: List[str], rate_matrix_path: str,
-                          num_replicates: int = 100, random_seed: int = 0, quantization_grid_center: float = 0.03,
-                          quantization_grid_step: float = 1.1, quantization_grid_num_steps: int = 64,
-                          output_support_dir: Optional[str] = None, _version="1") -> None:
-    """Felsenstein's bootstrap support of every internal edge of `<tree_dir>/<family>.txt` from `num_replicates`
-    neighbour-joining trees of resampled sites, on the GPU (`bootstrap_supports`).  The distances are the maximum-likelihood
-    grid points (center, step, num_steps) under the rate matrix at the family's site rates `<site_rates_dir>/<family>.txt`:
-    the rate categories are the unique values of that file, and D = grid[index] with no mean-rate factor, because the file's
-    rates are already normalised.  The resampling seed of a family is `support_seeds(families, random_seed)`'s, so its result
-    depends on its name and the seed alone.  Per family:
-    `<output_support_dir>/<family>.txt`: the header `node bootstrap`, then one line `name share` per internal non-root node in
-    `tree.nodes()` order (the share of the replicates whose tree has the split of the edge above the node);
-    `<output_support_dir>/<family>.profiling`.
-    Site rates are not re-estimated per replicate: a site keeps its rate when it is drawn."""
+def _stage_families(tree_dir: str, msa_dir: str, site_rates_dir: str, families: List[str], rate_matrix_path: str, random_seed: int,
+                    quantization_grid_center: float, quantization_grid_step: float, quantization_grid_num_steps: int):
+    """what the bootstrap stages (`nj_bootstrap_supports`, `nj_transfer_supports`) read per family, in the families' order:
+    (family, seed, start time, seconds for the bank, device, tree, leaf names, seqs [n, L], logP, site_to_rate, grid)"""
     from ..counting._host import read_msa, read_site_rates
     from ..counting._stage import _device_index
     from ..io import read_rate_matrix
-    if output_support_dir is None:
-        raise ValueError("output_support_dir is required")
-    if _lib.load().cb_device_count() <= 0:
-        raise _lib.CherryBankError("nj_bootstrap_supports: no HIP device visible; the bootstrap runs on the MI355X only "
-                                   "(no CPU fallback)")
-    os.makedirs(output_support_dir, exist_ok=True)
     rm = read_rate_matrix(rate_matrix_path)
     alphabet = [str(c) for c in rm.columns]
     Q = np.ascontiguousarray(rm.to_numpy(), dtype=np.float64)
@@ -271,9 +257,35 @@ def nj_bootstrap_supports(tree_dir: str, msa_dir: str, site_rates_dir: str, fami
         seqs = lut[np.frombuffer(text, dtype=np.uint8)].reshape(len(names), len(rates))
         unique_rates, s2r = np.unique(rates, return_inverse=True)
         logP = compute_log_transition_matrices(Q, grid, unique_rates, device=dev)
-        t_bank = time.time() - st
+        yield family, seed, st, time.time() - st, dev, tree, names, seqs, logP, s2r.astype(np.int32), grid
+
+
+@cached_computation(output_dirs=["output_support_dir"])
+def nj_bootstrap_supports(tree_dir: str, msa_dir: str, site_rates_dir: str, families: List[str], rate_matrix_path: str,
+                          num_replicates: int = 100, random_seed: int = 0, quantization_grid_center: float = 0.03,
+                          quantization_grid_step: float = 1.1, quantization_grid_num_steps: int = 64,
+                          output_support_dir: Optional[str] = None, _version="1") -> None:
+    """Felsenstein's bootstrap support of every internal edge of `<tree_dir>/<family>.txt` from `num_replicates`
+    neighbour-joining trees of resampled sites, on the GPU (`bootstrap_supports`).  The distances are the maximum-likelihood
+    grid points (center, step, num_steps) under the rate matrix at the family's site rates `<site_rates_dir>/<family>.txt`:
+    the rate categories are the unique values of that file, and D = grid[index] with no mean-rate factor, because the file's
+    rates are already normalised.  The resampling seed of a family is `support_seeds(families, random_seed)`'s, so its result
+    depends on its name and the seed alone.  Per family:
+    `<output_support_dir>/<family>.txt`: the header `node bootstrap`, then one line `name share` per internal non-root node in
+    `tree.nodes()` order (the share of the replicates whose tree has the split of the edge above the node);
+    `<output_support_dir>/<family>.profiling`.
+    Site rates are not re-estimated per replicate: a site keeps its rate when it is drawn."""
+    if output_support_dir is None:
+        raise ValueError("output_support_dir is required")
+    if _lib.load().cb_device_count() <= 0:
+        raise _lib.CherryBankError("nj_bootstrap_supports: no HIP device visible; the bootstrap runs on the MI355X only "
+                                   "(no CPU fallback)")
+    os.makedirs(output_support_dir, exist_ok=True)
+    for family, seed, st, t_bank, dev, tree, names, seqs, logP, s2r, grid in _stage_families(
+            tree_dir, msa_dir, site_rates_dir, families, rate_matrix_path, random_seed, quantization_grid_center,
+            quantization_grid_step, quantization_grid_num_steps):
         prof: Dict[str, float] = {}
-        nodes, support = bootstrap_supports(tree, names, seqs, logP, s2r.astype(np.int32), grid, int(num_replicates), seed,
+        nodes, support = bootstrap_supports(tree, names, seqs, logP, s2r, grid, int(num_replicates), seed,
                                             device=dev, profile=prof)
         write_bootstrap_supports(os.path.join(output_support_dir, family + ".txt"), tree.nodes(), nodes, support)
         with open(os.path.join(output_support_dir, family + ".profiling"), "w") as fh:

@@ -487,6 +487,27 @@ int cb_nj_batch(int device, int n_fam, const int *n, const double *D, int *join_
 int cb_boot_nj(int device, int S, int T, int R, const double *logP, const double *grid, const int8_t *seqs, int n, int L,
                const int *site_to_rate, int n_rep, uint64_t seed, const double *weights, int *join_nodes, double *join_len,
                int *final_nodes, double *final_D, int *index, double *weights_out, double *kernel_ms);
+/* Transfer distances of reference splits to the trees of bootstrap replicates (Lemoine et al. 2018, the transfer bootstrap
+ * expectation), on the device.  Leaves are 0 .. n - 1.  ref_sets [n_ref][ceil(n / 8)]: the leaf sets A_r, each one side (either)
+ * of an edge of the reference tree, packed as tree_splits packs them: leaf k is bit 0x80 >> (k & 7) of byte k >> 3, pad bits 0;
+ * p_r = min(|A_r|, n - |A_r|) >= 2.  join_nodes [n_rep][n - 3][2]: the join records of cb_nj_batch / cb_boot_nj; the node join q
+ * makes is n + q, its leaf set S_{b,q} is the union of its two members' sets, and leaf v has the set {v}.  With
+ *     h(A, S) = |A xor S|,   d(A, S) = min(h, n - h)                      (either side of either split)
+ *     delta[r][b] = min( p_r - 1 , min_q d(A_r, S_{b,q}) )                (integers)
+ * where p_r - 1 is the distance to the nearest leaf edge of the replicate's tree (those edges are not in the join records, and
+ * the three final nodes add no new split), the outputs are
+ *   min_dist [n_ref][n_rep] (may be NULL): delta;
+ *   sum_dist [n_ref]: sum_b delta[r][b];   present [n_ref]: the number of b with delta[r][b] = 0 -- the replicates whose tree
+ *   has the split itself, since p_r >= 2.  The caller's support is 1 - sum_dist[r] / (n_rep (p_r - 1));
+ *   kernel_ms [2] (may be NULL): GPU time of building the replicates' leaf sets and of the distances, by HIP events.
+ * The replicates go in chunks of whole replicates under 512 MiB of resident leaf sets (a replicate alone above that runs alone);
+ * a replicate's column of delta depends neither on n_rep nor on the chunks.  Every argument is validated on the host before any
+ * device work (CB_EINVAL, naming the argument and the value): a NULL pointer other than min_dist and kernel_ms, n < 4, an n whose
+ * matrix passes 2^31 - 1 entries (cb_nj_batch's bound), n_ref < 1, n_rep < 1, a reference row with a pad bit set or with p < 2
+ * (empty, full, one leaf, all but one), a join member outside [0, n + q), a node that is a member twice.  No device visible:
+ * CB_EHIP. */
+int cb_transfer_support(int device, int n, int n_ref, const uint8_t *ref_sets, int n_rep, const int *join_nodes, int *min_dist,
+                        long long *sum_dist, int *present, double *kernel_ms);
 
 /* ---- held-out log-likelihood of ONE family under one model (tail of SURVEY 8f #4) ---------------
  * Replaces the per-(node, site) python loops of cherryml/evaluation/_likelihood.py:47-327
