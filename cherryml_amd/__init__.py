@@ -17,6 +17,8 @@ from .phylogeny_estimation import (bootstrap_nj_records, bootstrap_supports, nj_
                                    splits_of_join_records, tree_splits)
 from .phylogeny_estimation import (nj_transfer_supports, read_transfer_supports, transfer_bootstrap_supports,  # noqa: F401,E402
                                    transfer_distances, transfer_supports_of_records, write_transfer_supports)
+from .phylogeny_estimation import (bootstrap_tree, read_ufboot_supports, ufboot_supports,  # noqa: F401,E402
+                                   write_ufboot_supports)
 from ._cherryml_public_api import cherryml_public_api  # noqa: F401,E402
 from .simulation import simulate_msas  # noqa: F401,E402
 from .estimation import (EStep, RateMatrix, RateMatrixLearner, em_lg, jtt_ipw, quantized_transitions_mle,  # noqa: F401
@@ -37,4 +39,5 @@ __all__ = [
     "bootstrap_nj_records", "bootstrap_supports", "nj_bootstrap_supports", "splits_of_join_records", "tree_splits",
     "transfer_distances", "transfer_supports_of_records", "transfer_bootstrap_supports", "nj_transfer_supports",
     "read_transfer_supports", "write_transfer_supports",
+    "bootstrap_tree", "ufboot_supports", "read_ufboot_supports", "write_ufboot_supports",
 ]

@@ -90,6 +90,7 @@ SIGNATURES = {
     "cb_bl_nni_scan": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cb_bl_ancestral": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "cb_bl_supports": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cb_bl_bootstrap_best": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cb_bl_destroy": (C.c_int, [_vp]),
     "cb_tree_site_rates": (C.c_int, [C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp]),

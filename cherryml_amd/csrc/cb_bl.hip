@@ -1,13 +1,15 @@
 // libcherrybank: maximum-likelihood branch lengths on fixed trees by EM, on a resident handle (bl.hip.h; include/cherrybank.h,
 // cb_bl_*), the nearest-neighbour-interchange scan on the handle's resident messages (nni.hip.h; cb_bl_nni_scan) and the marginal
 // ancestral reconstruction from the same messages (anc.hip.h; cb_bl_ancestral) and the local branch supports by resampling the
-// scan's per-site log-likelihoods (sup.hip.h; cb_bl_supports).
+// scan's per-site log-likelihoods (sup.hip.h; cb_bl_supports) and the best resampled candidate per bootstrap replicate among a
+// tree and its NNI neighbours (ufb.hip.h; cb_bl_bootstrap_best).
 #include "cb_internal.hip.h"
 #include "common.hip.h"
 #include "bl.hip.h"
 #include "nni.hip.h"
 #include "anc.hip.h"
 #include "sup.hip.h"
+#include "ufb.hip.h"
 #include "em_host.hip.h"
 
 struct cb_bl_s {
@@ -484,7 +486,134 @@ extern "C" int cb_bl_supports(cb_bl_s *h, int n_rep, const uint64_t *seeds, cons
   return CB_OK;
 }
 
-constexpr size_t ANC_POST_BYTES = (size_t)256 << 20;   // post[node][unit][S] of one chunk of nodes, at most (one node always goes);
+constexpr size_t UFB_BYTES = (size_t)256 << 20;   // ll'[move][unit] of one chunk of moves, at most (one tile of 16 moves always
+                                                  // goes); the test hook CB_UFB_BYTES: the results do not depend on the chunking
+constexpr int UFB_WORKGROUPS = 1024;              // the product's launch aims at this many workgroups: four per CU
+
+extern "C" int cb_bl_bootstrap_best(cb_bl_s *h, int n_rep, const uint64_t *seeds, const int *n_moves, const int *moves,
+                                    double *best_score, int *best_code, double *base, double *fam_ll, double *kernel_ms) {
+  static const char *who = "cb_bl_bootstrap_best";
+  if (!h) return fail(CB_EINVAL, "%s: NULL handle", who);
+  if (!n_moves || !seeds || !best_score || !best_code) return fail(CB_EINVAL, "%s: NULL argument", who);
+  if (n_rep < 1 || n_rep > SUP_MAX_REP) return fail(CB_EINVAL, "%s: n_rep = %d (1 <= replicates <= %d)", who, n_rep, SUP_MAX_REP);
+  // every triple and every incoming score, on the host, before any device work
+  const EmForestHost &H = h->forest.host;
+  const int n_fam = H.n_fam(), S = h->forest.S;
+  std::vector<size_t> off_m(n_fam + 1, 0);
+  for (int f = 0; f < n_fam; ++f) {
+    if (n_moves[f] < 0) return fail(CB_EINVAL, "%s: family %d: n_moves = %d", who, f, n_moves[f]);
+    off_m[f + 1] = off_m[f] + n_moves[f];
+  }
+  if (off_m[n_fam] > 0 && !moves) return fail(CB_EINVAL, "%s: NULL argument", who);
+  const size_t bound = cb_hook_bytes("CB_UFB_BYTES", UFB_BYTES);
+  const int rep_tiles = (n_rep + UFB_RT - 1) / UFB_RT;
+  std::vector<int> chunk(n_fam, 0);
+  size_t max_moves = 0, max_out = 0, max_units = 0, max_slices = 1;
+  for (int f = 0; f < n_fam; ++f) {
+    const EmFamHost &F = H.fam[f];
+    const int rc_f = bl_check_moves(who, H, f, n_moves[f], moves + 3 * off_m[f]);
+    if (rc_f != CB_OK) return rc_f;
+    for (int r = 0; r < n_rep; ++r)
+      if (std::isnan(best_score[(size_t)f * n_rep + r]))
+        return fail(CB_EINVAL, "%s: family %d replicate %d: the incoming best score is NaN", who, f, r);
+    max_units = std::max(max_units, (size_t)F.n_units);
+    if (n_moves[f] == 0) continue;
+    // chunks of whole move tiles: the byte bound, and the scan's launch below 2^31 blocks
+    const size_t n_blocks = ((size_t)F.n_units + 64 / S - 1) / (64 / S);
+    const size_t fit = std::max<size_t>(bound / ((size_t)F.n_units * sizeof(double)) / 16 * 16, 16);
+    const size_t launch = (size_t)INT32_MAX / n_blocks;
+    if (launch < 1) return fail(CB_EINVAL, "%s: family %d: %zu site tiles (at most 2^31 - 1 per launch)", who, f, n_blocks);
+    chunk[f] = (int)std::min<size_t>(n_moves[f], std::min(fit, launch));
+    max_moves = std::max(max_moves, (size_t)n_moves[f]);
+    max_out = std::max(max_out, (size_t)chunk[f] * F.n_units);
+    max_slices = std::max(max_slices, std::min<size_t>(((size_t)chunk[f] + 15) / 16, std::max(1, UFB_WORKGROUPS / rep_tiles)));
+  }
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0.0;
+  HIP_TRY(hipSetDevice(h->forest.device));
+  // the messages and l_u of every family at the current indices: after a round the resident ones are its start's
+  CbKernelTimer passes(kernel_ms != nullptr, h->ev[0], h->ev[1]);
+  int rc = passes.begin(false);
+  if (rc != CB_OK) return rc;
+  for (int f = 0; f < n_fam; ++f) bl_launch_passes(h, f, true);
+  HIP_TRY(hipGetLastError());
+  if ((rc = passes.end(kernel_ms)) != CB_OK) return rc;
+  std::vector<int> inv(max_units);
+  CbDevBufs bufs;   // this call's: freed on every return path
+  int *dmoves = bufs.up<int>(nullptr, 3 * max_moves, rc), *dinv = bufs.up<int>(nullptr, max_units, rc);
+  double *dout = bufs.up<double>(nullptr, max_out, rc), *ddelta = bufs.up<double>(nullptr, max_moves, rc);
+  double *dW = bufs.up<double>(nullptr, (size_t)n_rep * max_units, rc), *dbase = bufs.up<double>(nullptr, n_rep, rc);
+  double *dpart = bufs.up<double>(nullptr, max_slices * n_rep, rc), *dbest = bufs.up<double>(nullptr, n_rep, rc);
+  int *dpcode = bufs.up<int>(nullptr, max_slices * n_rep, rc), *dcode = bufs.up<int>(nullptr, n_rep, rc);
+  if (rc != CB_OK) return rc;
+  for (int f = 0; f < n_fam; ++f) {
+    const EmFamView w = h->forest.view(f);
+    const EmFamHost &F = w.F;
+    const int U = F.n_units;
+    for (int k = 0; k < U; ++k) inv[F.perm[k]] = k;
+    if (n_moves[f] > 0)
+      HIP_TRY(hipMemcpy(dmoves, moves + 3 * off_m[f], 3 * (size_t)n_moves[f] * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dinv, inv.data(), (size_t)U * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dbest, best_score + (size_t)f * n_rep, (size_t)n_rep * sizeof(double), hipMemcpyHostToDevice));
+    // the multiplicities of every replicate, once per family, and the tree's own resampled log-likelihood
+    SupWeightArgs wa{};
+    wa.n_units = U; wa.k0 = (uint32_t)(seeds[f] & 0xFFFFFFFFu); wa.k1 = (uint32_t)(seeds[f] >> 32); wa.inv = dinv; wa.W = dW;
+    UfbGemmArgs ga{};
+    ga.n_rep = n_rep; ga.n_units = U; ga.out = dout; ga.ll = w.ll; ga.W = dW; ga.base = dbase; ga.part_score = dpart;
+    ga.part_code = dpcode;
+    UfbMergeArgs ma{};
+    ma.n_rep = n_rep; ma.first = 1; ma.base = dbase; ma.part_score = dpart; ma.part_code = dpcode; ma.best_score = dbest;
+    ma.best_code = dcode;
+    const unsigned merge_grid = (unsigned)((n_rep + 255) / 256);
+    {
+      CbKernelTimer draw(kernel_ms != nullptr, h->ev[0], h->ev[1]);
+      double ms = 0.0;
+      if ((rc = draw.begin(false)) != CB_OK) return rc;
+      hipLaunchKernelGGL(sup_weights_kernel, dim3((unsigned)n_rep), dim3(256), 0, 0, wa);
+      hipLaunchKernelGGL(ufb_gemm_kernel<true>, dim3((unsigned)rep_tiles), dim3(256), 0, 0, ga, rep_tiles);
+      if (n_moves[f] == 0) hipLaunchKernelGGL(ufb_merge_kernel, dim3(merge_grid), dim3(256), 0, 0, ma);   // the tree against the incoming best
+      HIP_TRY(hipGetLastError());
+      if ((rc = draw.end(&ms)) != CB_OK) return rc;
+      if (kernel_ms) kernel_ms[2] += ms;
+    }
+    NniArgs a{};
+    a.S = S; a.n_units = U; a.n_cats = F.n_cats; a.root = F.root; a.n_blocks = w.n_blocks;
+    a.parent = w.parent; a.child_ptr = w.child_ptr; a.child_idx = w.child_idx; a.qb = w.qb; a.unit_cat = w.unit_cat; a.P = h->dP;
+    a.pi_root = h->dpi; a.msg = w.msg; a.U = w.U; a.ll = w.ll; a.out = dout;
+    for (int m0 = 0; m0 < n_moves[f]; m0 += chunk[f]) {
+      const int nm = std::min(chunk[f], n_moves[f] - m0);
+      a.moves = dmoves + 3 * (size_t)m0;
+      a.delta = ddelta + m0;
+      ga.n_moves = nm; ga.move0 = m0; ga.delta = a.delta; ga.n_tiles = (nm + 15) / 16;
+      ga.n_slices = std::min(ga.n_tiles, std::max(1, UFB_WORKGROUPS / rep_tiles));
+      ma.n_slices = ga.n_slices; ma.first = m0 == 0;
+      CbKernelTimer scan(kernel_ms != nullptr, h->ev[0], h->ev[2], h->ev[1]);
+      double ms[2] = {0.0, 0.0};
+      if ((rc = scan.begin(false)) != CB_OK) return rc;
+      hipLaunchKernelGGL(nni_scan_kernel, dim3((unsigned)nm * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
+      hipLaunchKernelGGL(nni_sum_kernel, dim3((unsigned)nm), dim3(64), 0, 0, a);
+      if ((rc = scan.lap()) != CB_OK) return rc;
+      hipLaunchKernelGGL(ufb_gemm_kernel<false>, dim3((unsigned)(ga.n_slices * rep_tiles)), dim3(256), 0, 0, ga, rep_tiles);
+      hipLaunchKernelGGL(ufb_merge_kernel, dim3(merge_grid), dim3(256), 0, 0, ma);
+      HIP_TRY(hipGetLastError());
+      if ((rc = scan.end(ms)) != CB_OK) return rc;
+      if (kernel_ms) kernel_ms[1] += ms[0], kernel_ms[2] += ms[1];
+      // (the next chunk writes the same buffers: stream order puts it behind this chunk's kernels)
+    }
+    HIP_TRY(hipMemcpy(best_score + (size_t)f * n_rep, dbest, (size_t)n_rep * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(best_code + (size_t)f * n_rep, dcode, (size_t)n_rep * sizeof(int), hipMemcpyDeviceToHost));
+    if (base) HIP_TRY(hipMemcpy(base + (size_t)f * n_rep, dbase, (size_t)n_rep * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  // dll now holds l_u at the current indices -- the bits cb_bl_get's inside pass would write
+  std::vector<char> stale(n_fam);
+  for (int f = 0; f < n_fam; ++f) stale[f] = !h->ll_fresh[f];
+  rc = bl_read_ll(h, stale, nullptr);
+  if (rc != CB_OK) return rc;
+  std::fill(h->ll_fresh.begin(), h->ll_fresh.end(), 1);
+  if (fam_ll) std::copy(h->fam_ll.begin(), h->fam_ll.end(), fam_ll);
+  return CB_OK;
+}
+
+constexpr size_t ANC_POST_BYTES =(size_t)256 << 20;   // post[node][unit][S] of one chunk of nodes, at most (one node always goes);
                                                        // the test hook CB_ANC_POST_BYTES: the results do not depend on the chunking
 
 extern "C" int cb_bl_ancestral(cb_bl_s *h, int8_t *state, double *conf, double *post, double *fam_ll, double *kernel_ms) {

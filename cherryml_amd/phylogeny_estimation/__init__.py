@@ -13,7 +13,9 @@ by resampling the scan's per-site log-likelihoods on the GPU (`BranchLengthFitte
 `ml_branch_supports`); Felsenstein's bootstrap of the neighbour-joining tree, the resampled distances as one matrix product per pair
 of sequences and the joins on the GPU (`bootstrap_nj_records`, `bootstrap_supports`, the stage `nj_bootstrap_supports`); the transfer bootstrap of the same replicates, every split of the tree against every split of
 every replicate by xor and popcount on the GPU (`transfer_distances`, `transfer_bootstrap_supports`, the stage
-`nj_transfer_supports`)."""
+`nj_transfer_supports`); bootstrap supports from the NNI search's own trees, the best resampled candidate of every replicate kept
+on the GPU while the search runs (`BranchLengthFitter.bootstrap_best`, `ufboot_supports`, the `output_bootstrap_dir` of
+`ml_nni_trees` / `nj_nni_trees`)."""
 from ._ble import (  # noqa: F401
     BleBank,
     branch_lengths,
@@ -58,3 +60,4 @@ from ._transfer import (  # noqa: F401,E402
     transfer_supports_of_records,
     write_transfer_supports,
 )
+from ._ufboot import bootstrap_tree, read_ufboot_supports, ufboot_supports, write_ufboot_supports  # noqa: F401,E402

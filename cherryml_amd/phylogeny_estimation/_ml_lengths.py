@@ -10,7 +10,8 @@ directories, `nj_ml_trees` the tree estimator `nj_trees` + `ml_branch_lengths`.
 The handle also scores the nearest-neighbour interchanges of its trees from the messages its passes leave resident (`nni_moves`,
 `nni_scan`; the search on top of them is `_nni.py`) and reconstructs the marginal posterior of the state at
 every node from the same messages (`ancestral_states`; the stage is `_ancestral.py`), and resamples the
-scan's per-site log-likelihoods into local branch supports (`branch_supports`; the stage is `_supports.py`).
+scan's per-site log-likelihoods into local branch supports (`branch_supports`; the stage is `_supports.py`)
+and into the best candidate of every bootstrap replicate (`bootstrap_best`; `_ufboot.py`).
 
 Out of scope: changing a handle's topology in place, a continuous (off-grid) optimiser, S > 32."""
 import ctypes
@@ -60,6 +61,7 @@ class BranchLengthFitter(_lib.ResidentHandle):
         self.last_nni_kernel_ms = (0.0, 0.0)   # (passes, scan) of the last nni_scan
         self.last_ancestral_kernel_ms = (0.0, 0.0)   # (passes, reconstruction) of the last ancestral_states
         self.last_support_kernel_ms = (0.0, 0.0, 0.0)   # (passes, scan, resampling) of the last branch_supports
+        self.last_ufboot_kernel_ms = (0.0, 0.0, 0.0)   # (passes, scan, resampling and reduction) of the last bootstrap_best
         self._create()
 
     def _create(self) -> None:
@@ -184,6 +186,53 @@ class BranchLengthFitter(_lib.ResidentHandle):
             out.append([x.reshape(int(k), num_replicates)
                         for x, k in zip(np.split(rep, np.cumsum(n_moves.astype(np.int64))[:-1] * num_replicates), n_moves)])
         return [tuple(x[k] for x in out) for k in range(len(moves))]
+
+    def bootstrap_best(self, num_replicates: int = 1000, seeds: Optional[Sequence[int]] = None, best: Optional[Sequence] = None,
+                       moves: Optional[Sequence] = None, base: bool = False):
+        """Per bootstrap replicate the best resampled log-likelihood among a running best, this handle's tree and its
+        nearest-neighbour interchanges at the current indices, and which of them attains it (`cb_bl_bootstrap_best`; DESIGN.md
+        section 24) -> per family (score [R], code [R]) and with `base` also the tree's own resampled log-likelihood B [R].
+        Replicate r of a family is replicate r of `branch_supports` with the same seed.  The candidates of a replicate, in
+        order: the incoming `best[k][r]` (code -2; `best=None` means -inf, a first call), the tree (code -1, score B^r), move m
+        of the family's list (code m, score B^r + delta_rep[m][r] of `branch_supports`; a move whose delta is not finite is left
+        out); the result is the largest score and the FIRST candidate that attains it.  `moves`: per family its own [n, 3] list
+        in place of `nni_moves()`, in any order.  Feeding a call's scores to the next handle's call as `best` carries the
+        running best through a search (`_ufboot.py`).  Changes nothing `round()`, `indices()`, `log_likelihoods()`,
+        `nni_scan()`, `branch_supports()` or `ancestral_states()` return.  Sets `last_ufboot_kernel_ms` = (passes, scan,
+        resampling and reduction)."""
+        n_fam = self.n_nodes.size
+        num_replicates = int(num_replicates)
+        R = max(num_replicates, 0)
+        seeds = [0] * n_fam if seeds is None else [int(s) for s in seeds]
+        if len(seeds) != n_fam:
+            raise ValueError(f"bootstrap_best: {len(seeds)} seeds for {n_fam} families")
+        seed_arr = np.array([s & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=np.uint64)
+        moves = self.nni_moves() if moves is None else [np.ascontiguousarray(m, dtype=np.int32).reshape(-1, 3) for m in moves]
+        if len(moves) != n_fam:
+            raise ValueError(f"bootstrap_best: {len(moves)} move lists for {n_fam} families")
+        if best is None:
+            score = np.full((n_fam, R), -np.inf)
+        else:
+            if len(best) != n_fam:
+                raise ValueError(f"bootstrap_best: {len(best)} incoming arrays for {n_fam} families")
+            score = np.ascontiguousarray(np.stack([np.asarray(b, dtype=np.float64).reshape(-1) for b in best]) if R else
+                                         np.zeros((n_fam, 0)))
+            if score.shape != (n_fam, R):
+                raise ValueError(f"bootstrap_best: the incoming best has shape {score.shape}, not {(n_fam, R)}")
+        n_moves = np.array([len(m) for m in moves], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(moves).reshape(-1), dtype=np.int32)
+        code = np.empty((n_fam, R), dtype=np.int32)
+        own = np.empty((n_fam, R)) if base else None
+        ms = (ctypes.c_double * 3)(0.0, 0.0, 0.0)
+        rc = _lib.load().cb_bl_bootstrap_best(self._handle(), num_replicates, seed_arr.ctypes.data, n_moves.ctypes.data,
+                                              flat.ctypes.data, score.ctypes.data, code.ctypes.data,
+                                              own.ctypes.data if base else None, None, ctypes.addressof(ms))
+        if rc == _lib.CB_EINVAL:   # a refused call: the library's message names the value
+            raise _lib.CherryBankError(f"cb_bl_bootstrap_best failed ({rc}): "
+                                       f"{_lib.load().cb_last_error().decode('utf-8', 'replace')}")
+        _lib.check(rc, "cb_bl_bootstrap_best")
+        self.last_ufboot_kernel_ms = (ms[0], ms[1], ms[2])
+        return [(score[k], code[k], own[k]) if base else (score[k], code[k]) for k in range(n_fam)]
 
     def ancestral_states(self, posteriors: bool = False):
         """The marginal posterior of the state at EVERY node (root, internal nodes, leaves) at the current indices

@@ -100,7 +100,9 @@ def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: Lis
                  num_nni_rounds: int = 10, num_rounds: int = 10, quantization_grid_center: float = 0.03,
                  quantization_grid_step: float = 1.1, quantization_grid_num_steps: int = 64, output_tree_dir: Optional[str] = None,
                  output_likelihood_dir: Optional[str] = None, max_bank_bytes: int = DEFAULT_MAX_BANK_BYTES,
-                 output_support_dir: Optional[str] = None, num_support_replicates: int = 1000, _version="1") -> None:
+                 output_support_dir: Optional[str] = None, num_support_replicates: int = 1000,
+                 output_bootstrap_dir: Optional[str] = None, num_bootstrap_replicates: int = 1000, bootstrap_seed: int = 0,
+                 _version="1") -> None:
     """Improve the topologies of `<tree_dir>/<family>.txt` by likelihood: at most `num_nni_rounds` times, per family, fit the
     lengths of the current tree (`BranchLengthFitter`, at most `num_rounds` EM rounds), score ALL its nearest-neighbour
     interchanges (`nni_scan`), select those of positive gain at disjoint places (`select_nni`) and apply them (`apply_nni`).
@@ -116,13 +118,22 @@ def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: Lis
     `output_support_dir`, also `<output_support_dir>/<family>.txt` as `ml_branch_supports` writes it: the aLRT, SH-like and RELL
     supports of the FINAL tree's internal edges from `num_support_replicates` site resamples (seed
     `simulation.family_seed(family, 0)`), computed on the last handle that holds the final tree at its final lengths; without
-    it (the default) nothing else is written or computed."""
+    it (the default) nothing else is written or computed.  With `output_bootstrap_dir`, also the bootstrap supports of the
+    FINAL tree's internal edges from the search's own trees (`_ufboot.py`; UFBoot's idea, not IQ-TREE's
+    arithmetic): on every handle on which the family's tree is accepted, after its EM rounds, `bootstrap_best` scores that tree
+    and all its NNI neighbours under `num_bootstrap_replicates` site resamples (seed `simulation.family_seed(family,
+    bootstrap_seed)`) against the running best of every replicate; `<output_bootstrap_dir>/<family>.txt` holds the header
+    `node ufboot` and per internal non-root node of the final tree, in `tree.nodes()` order, the share of the replicates whose
+    best tree has the split of the edge above it, `<family>.choices` per contributing handle
+    `<t> <nni_round> <candidates> <replicates won by the tree> <replicates won by its neighbours>`.  A family's file does not
+    depend on its batch; without the directory (the default) every other file is byte for byte what it is with it."""
     from ..counting._host import read_msa, read_site_rates
     from ..counting._stage import _device_index
     from ..evaluation._likelihood import (_family_units, _stationary_distribution, dp_likelihood_computation_batch,
                                           write_log_likelihood)
     from ..io import read_rate_matrix
     from ._supports import support_seeds, supports_of_trees, write_supports
+    from ._ufboot import choices_lines, ufboot_supports, update_choice, write_ufboot_supports
     if output_tree_dir is None or output_likelihood_dir is None:
         raise ValueError("output_tree_dir and output_likelihood_dir are required")
     if _lib.load().cb_device_count() <= 0:
@@ -150,6 +161,14 @@ def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: Lis
             for _ in families]
     final_ll: List[Optional[float]] = [None] * F
     supports: List[Optional[tuple]] = [None] * F   # (with output_support_dir) the final trees' supports
+    # (with output_bootstrap_dir) per family: the running best score of every replicate, the (t, code) it chose, the contributing
+    # trees and per contribution its NNI round and its number of candidates
+    n_boot = int(num_bootstrap_replicates)
+    ufb_best: List[Optional[np.ndarray]] = [None] * F
+    ufb_choice = [(np.full(max(n_boot, 0), -1, dtype=np.int64), np.full(max(n_boot, 0), -2, dtype=np.int64)) for _ in families]
+    contributions: List[List[Tree]] = [[] for _ in families]
+    ufb_rounds: List[List[int]] = [[] for _ in families]
+    ufb_cands: List[List[int]] = [[] for _ in families]
     bank_bytes = [2 * grid.size * np.unique(r).size * Q.size * 8 for r in rates]
     # Per family: rnd = its NNI round; trees[f] = the tree the next handle takes -- the input, or a candidate (fitted[f] with the
     # moves sel[f] applied) that has to beat before[f].  ONE handle per pass over the work list: on a candidate its
@@ -205,6 +224,22 @@ def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: Lis
                         for k, f in enumerate(fams):
                             if ends[k]:
                                 supports[f] = sup[k]
+                ufb = None
+                if output_bootstrap_dir is not None and go.any():
+                    # every family whose tree on this handle is accepted contributes it and all its neighbours; a refused
+                    # candidate meets an incoming best of +inf, which nothing beats, and its result is dropped
+                    all_moves = fit.nni_moves()
+                    st_ufb = time.time()
+                    ufb = fit.bootstrap_best(n_boot, seeds=support_seeds([families[f] for f in fams], bootstrap_seed),
+                                             best=[(np.full(n_boot, -np.inf) if ufb_best[f] is None else ufb_best[f]) if go[k]
+                                                   else np.full(n_boot, np.inf) for k, f in enumerate(fams)],
+                                             moves=[m if g else m[:0] for m, g in zip(all_moves, go)])
+                    for f in fams:                             # (shares of the batch; these keys exist only with the bootstrap)
+                        prof[f]["bootstrap_time"] = prof[f].get("bootstrap_time", 0.0) + (time.time() - st_ufb) / len(fams)
+                        prof[f]["bootstrap_kernel_ms"] = (prof[f].get("bootstrap_kernel_ms", 0.0)
+                                                          + fit.last_ufboot_kernel_ms[2] / len(fams))
+                        prof[f]["bootstrap_scan_kernel_ms"] = (prof[f].get("bootstrap_scan_kernel_ms", 0.0)   # its own passes and scan
+                                                               + sum(fit.last_ufboot_kernel_ms[:2]) / len(fams))
             for k, f in enumerate(fams):
                 for key, x in (("create_time", t_create), ("scan_time", t_scan), ("scan_kernel_ms", ms_scan),
                                ("fit_time", time.time() - st)):
@@ -223,6 +258,12 @@ def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: Lis
                 t.add_nodes(trees[f].nodes())
                 t.add_edges([(u, v, lengths[k][v]) for u, v, _ in trees[f].edges()])
                 trees[f], ll = t, float(fam_ll[k])
+                if ufb is not None:
+                    ufb_best[f] = ufb[k][0]
+                    update_choice(ufb_choice[f], len(contributions[f]), ufb[k][1])
+                    contributions[f].append(t)
+                    ufb_rounds[f].append(rnd[f])
+                    ufb_cands[f].append(1 + len(all_moves[k]))
                 if not want[k]:                                # the topology of the last round's moves after its own EM rounds
                     final_ll[f] = ll
                     continue
@@ -249,6 +290,13 @@ def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: Lis
                 supports[f] = res
         for f, family in enumerate(families):
             write_supports(os.path.join(output_support_dir, family + ".txt"), list(trees[f].nodes()), supports[f])
+    if output_bootstrap_dir is not None:
+        os.makedirs(output_bootstrap_dir, exist_ok=True)
+        for f, family in enumerate(families):
+            nodes, share = ufboot_supports(trees[f], contributions[f], ufb_choice[f])
+            write_ufboot_supports(os.path.join(output_bootstrap_dir, family + ".txt"), list(trees[f].nodes()), nodes, share)
+            with open(os.path.join(output_bootstrap_dir, family + ".choices"), "w") as fh:
+                fh.write("".join(choices_lines(ufb_rounds[f], ufb_cands[f], ufb_choice[f])))
     st = time.time()
     lls = dp_likelihood_computation_batch(trees, msas, [None] * F, [[float(x) for x in r] for r in rates], alphabet, pi_root, Q,
                                           device=device)
@@ -268,13 +316,16 @@ def nj_nni_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, nu
                  output_site_rates_dir: Optional[str] = None, output_likelihood_dir: Optional[str] = None, remake=False,
                  quantization_grid_center=0.03, quantization_grid_step=1.1, quantization_grid_num_steps=64, verbose=True,
                  seed=1234, output_support_dir: Optional[str] = None, num_support_replicates: int = 1000,
-                 joiner="host") -> Dict[str, str]:
+                 joiner="host", output_bootstrap_dir: Optional[str] = None, num_bootstrap_replicates: int = 1000,
+                 bootstrap_seed: int = 0) -> Dict[str, str]:
     """`nj_trees` (with its `joiner`), then `ml_nni_trees` on its trees at its site rates and the same grid: `nj_ml_trees`'
     interface plus `num_nni_rounds`, and under `functools.partial` a `tree_estimator` of the end-to-end pipelines.  Returns the output
     directories: `output_tree_dir` / `output_likelihood_dir` hold the searched trees and their likelihoods,
     `output_site_rates_dir` is `nj_trees`' own.  Both stages are cached on their own.  With no cache directory the three output
     directories are required and the neighbour-joining trees and likelihoods go to their `nj_trees` subdirectories.  With
-    `output_support_dir` the supports of the final trees are written there (`ml_nni_trees`); the returned dict is the same."""
+    `output_support_dir` the supports of the final trees are written there (`ml_nni_trees`); the returned dict is the same.
+    With `output_bootstrap_dir` the bootstrap supports from the search's own trees are written there (`ml_nni_trees`,
+    `num_bootstrap_replicates`, `bootstrap_seed`); the returned dict is the same."""
     from ..caching import get_cache_dir
     from ._nj import nj_trees
     if _lib.load().cb_device_count() <= 0:
@@ -292,7 +343,9 @@ def nj_nni_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, nu
                   **nj_out)
     nj = nj if nj is not None else nj_out
     out = dict(output_tree_dir=output_tree_dir, output_likelihood_dir=output_likelihood_dir)
-    sup = dict(output_support_dir=output_support_dir, num_support_replicates=num_support_replicates)
+    sup = dict(output_support_dir=output_support_dir, num_support_replicates=num_support_replicates,
+               output_bootstrap_dir=output_bootstrap_dir, num_bootstrap_replicates=num_bootstrap_replicates,
+               bootstrap_seed=bootstrap_seed)
     ml = ml_nni_trees(tree_dir=nj["output_tree_dir"], msa_dir=msa_dir, site_rates_dir=nj["output_site_rates_dir"],
                       families=families, rate_matrix_path=rate_matrix_path, num_nni_rounds=num_nni_rounds, num_rounds=num_rounds,
                       **grid_args, **out, **sup)

@@ -707,7 +707,30 @@ int cb_em_destroy(cb_em h);
  *   group always goes) and every launch below 2^31 tiles (CB_EINVAL for a single group beyond that).  Fixed orders, no
  *   floating-point atomics: a move's delta_m^r is bitwise independent of the other moves, replicates, chunks and families, and
  *   the draws of replicate r do not depend on n_rep.  The call changes nothing cb_bl_round, cb_bl_get, cb_bl_nni_scan or
- *   cb_bl_ancestral return; its device buffers are its own, freed before it returns. */
+ *   cb_bl_ancestral return; its device buffers are its own, freed before it returns.
+ *
+ * cb_bl_bootstrap_best: per bootstrap replicate the best resampled log-likelihood among a running best, the handle's tree and its
+ *   nearest-neighbour interchanges at the CURRENT indices, and the candidate that attains it: the
+ *   reduction a search needs to keep, per replicate, the best tree it has met (UFBoot's idea).  One call, one family of
+ *   L = n_units sites.  l_u, ll'_m[u], d_m[u] and the replicate weights w_r[u] are exactly cb_bl_supports': the same Philox
+ *   counters, the same tag 0x53555050 and the same seed, so replicate r here is replicate r there.  B^r = sum_u w_r[u] l_u with
+ *   l_u taken as 0 where it is not finite; Delta_m^r = sum_u w_r[u] d_m[u]; a move whose delta_m is not finite is left out.  The
+ *   candidates of replicate r, in order:
+ *     code -2  the incoming best, best_score[f][r] as passed in (-inf on a first call)
+ *     code -1  the tree itself, score B^r
+ *     code  m  move m of the family's list, in its order, score fl(B^r + Delta_m^r)
+ *   Out: best_score [n_fam][n_rep] (in-out) the largest score and best_code [n_fam][n_rep] the code of the FIRST candidate that
+ *   attains it (strict >, in the order above); base (may be NULL) [n_fam][n_rep] the B^r.  A NaN in the incoming best_score is
+ *   refused (CB_EINVAL names family and replicate).  n_moves / moves as for cb_bl_nni_scan, validated in the same words; they
+ *   need not be grouped.  1 <= n_rep <= 65536 (CB_EINVAL names the value); seeds [n_fam].  fam_ll (may be NULL) [n_fam] the
+ *   log-likelihoods at the current indices; kernel_ms (may be NULL) [3]: the device time of the passes, of the scan and of the
+ *   resampling and reduction (weights, B, product-with-argmax, merge).  The passes of every family run first, then per family
+ *   the weights and B once, then per chunk of moves the scan, its sums (for the finiteness of delta_m) and the reduction; chunks
+ *   are whole tiles of 16 moves that keep ll' under 256 MiB.  Delta_m^r and B^r are accumulated as cb_bl_supports accumulates
+ *   delta_rep -- k from unit 0 up in steps of 4, zero operands past the ends -- so Delta_m^r is bitwise its delta_rep, and a tie
+ *   goes to the lowest code: the result does not depend on how moves, replicates or families are tiled, sliced or chunked.  A
+ *   family with no moves gets B^r against the incoming best.  No atomics.  The call changes nothing cb_bl_round, cb_bl_get,
+ *   cb_bl_nni_scan, cb_bl_supports or cb_bl_ancestral return; its device buffers are its own, freed before it returns. */
 #define CB_BL_MAX_CATS 64
 typedef struct cb_bl_s *cb_bl;
 int cb_bl_create(int device, int S, int T, const double *grid, const double *Q, const double *pi_root, int n_fam,
@@ -720,6 +743,8 @@ int cb_bl_nni_scan(cb_bl h, const int *n_moves, const int *moves, double *delta,
 int cb_bl_ancestral(cb_bl h, int8_t *state, double *conf, double *post, double *fam_ll, double *kernel_ms);
 int cb_bl_supports(cb_bl h, int n_rep, const uint64_t *seeds, const int *n_moves, const int *moves, double *alrt, int *sh_count,
                    int *rell_count, double *delta_rep, double *fam_ll, double *kernel_ms);
+int cb_bl_bootstrap_best(cb_bl h, int n_rep, const uint64_t *seeds, const int *n_moves, const int *moves, double *best_score,
+                         int *best_code, double *base, double *fam_ll, double *kernel_ms);
 int cb_bl_destroy(cb_bl h);
 
 /* ---- the maximum-likelihood rate category of every site on fixed full trees (S <= 32) ----------------------------------------
