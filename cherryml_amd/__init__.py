@@ -10,6 +10,7 @@ from .evaluation import compute_log_likelihoods  # noqa: F401,E402
 from .phylogeny_estimation import BranchLengthFitter, fast_cherries, ml_branch_lengths, nj_ml_trees, nj_trees  # noqa: F401,E402
 from .phylogeny_estimation import ml_lengths_and_site_rates, ml_site_rates, nj_ml_rates_trees, tree_site_rates  # noqa: F401,E402
 from .phylogeny_estimation import apply_nni, ml_nni_trees, nj_nni_trees, select_nni  # noqa: F401,E402
+from .phylogeny_estimation import apply_spr, ml_spr_trees, nj_spr_trees, select_spr  # noqa: F401,E402
 from .phylogeny_estimation import ml_ancestral_sequences  # noqa: F401,E402
 from .phylogeny_estimation import ml_branch_supports  # noqa: F401,E402
 from .phylogeny_estimation import neighbor_joining_device, neighbor_joining_device_batch  # noqa: F401,E402
@@ -35,6 +36,7 @@ __all__ = [
     "BranchLengthFitter", "ml_branch_lengths", "nj_ml_trees",
     "tree_site_rates", "ml_site_rates", "ml_lengths_and_site_rates", "nj_ml_rates_trees",
     "apply_nni", "select_nni", "ml_nni_trees", "nj_nni_trees", "ml_ancestral_sequences", "ml_branch_supports",
+    "apply_spr", "select_spr", "ml_spr_trees", "nj_spr_trees",
     "neighbor_joining_device", "neighbor_joining_device_batch",
     "bootstrap_nj_records", "bootstrap_supports", "nj_bootstrap_supports", "splits_of_join_records", "tree_splits",
     "transfer_distances", "transfer_supports_of_records", "transfer_bootstrap_supports", "nj_transfer_supports",

@@ -88,6 +88,7 @@ SIGNATURES = {
     "cb_bl_round": (C.c_int, [_vp, _vp, _vp, _vp]),
     "cb_bl_get": (C.c_int, [_vp, _vp, _vp, _vp]),
     "cb_bl_nni_scan": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cb_bl_spr_scan": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cb_bl_ancestral": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "cb_bl_supports": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cb_bl_bootstrap_best": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

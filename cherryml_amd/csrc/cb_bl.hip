@@ -2,11 +2,13 @@
 // cb_bl_*), the nearest-neighbour-interchange scan on the handle's resident messages (nni.hip.h; cb_bl_nni_scan) and the marginal
 // ancestral reconstruction from the same messages (anc.hip.h; cb_bl_ancestral) and the local branch supports by resampling the
 // scan's per-site log-likelihoods (sup.hip.h; cb_bl_supports) and the best resampled candidate per bootstrap replicate among a
-// tree and its NNI neighbours (ufb.hip.h; cb_bl_bootstrap_best).
+// tree and its NNI neighbours (ufb.hip.h; cb_bl_bootstrap_best) and the subtree prune-and-regraft scan on the same messages
+// (spr.hip.h; cb_bl_spr_scan).
 #include "cb_internal.hip.h"
 #include "common.hip.h"
 #include "bl.hip.h"
 #include "nni.hip.h"
+#include "spr.hip.h"
 #include "anc.hip.h"
 #include "sup.hip.h"
 #include "ufb.hip.h"
@@ -306,6 +308,173 @@ extern "C" int cb_bl_nni_scan(cb_bl_s *h, const int *n_moves, const int *moves, 
         if ((rc = scan.begin(false)) != CB_OK) return rc;
         hipLaunchKernelGGL(nni_scan_kernel, dim3((unsigned)nm * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
         hipLaunchKernelGGL(nni_sum_kernel, dim3((unsigned)nm), dim3(64), 0, 0, a);
+        HIP_TRY(hipGetLastError());
+        if ((rc = scan.end(&ms)) != CB_OK) return rc;
+        if (kernel_ms) kernel_ms[1] += ms;
+        // (the next chunk writes the same buffer: stream order puts it behind this chunk's sum)
+        if (ll_moves) {   // device (category) order -> the caller's unit order
+          HIP_TRY(hipMemcpy(host_out.data(), dout, (size_t)nm * U * sizeof(double), hipMemcpyDeviceToHost));
+          double *dst = ll_moves + off_o[f] + (size_t)m0 * U;
+          for (int m = 0; m < nm; ++m) em_unpermute(F.perm, host_out.data() + (size_t)m * U, dst + (size_t)m * U);
+        }
+      }
+      HIP_TRY(hipMemcpy(delta + off_m[f], ddelta, (size_t)n_moves[f] * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    // dll of the scanned families now holds l_u at the current indices -- the bits cb_bl_get's inside pass would write
+    std::vector<char> stale(n_fam);
+    for (int f = 0; f < n_fam; ++f) stale[f] = n_moves[f] > 0 && !h->ll_fresh[f];
+    rc = bl_read_ll(h, stale, nullptr);
+    if (rc != CB_OK) return rc;
+    for (int f = 0; f < n_fam; ++f)
+      if (stale[f]) h->ll_fresh[f] = 1;
+  }
+  if (fam_ll)
+    for (int f = 0; f < n_fam; ++f) fam_ll[f] = h->ll_fresh[f] ? h->fam_ll[f] : std::nan("");
+  return CB_OK;
+}
+
+// Move m of family f, (x, y, tau_s, tau_p, tau_y), on the host: what cb_bl_spr_scan refuses, and the move's step record for
+// spr_scan_kernel (spr.hip.h).  tau: the family's current indices; pos: n_nodes entries of -1, left so.
+static int bl_spr_record(const char *who, const EmForestHost &H, int f, int m, const int *mv, const int *tau, int T,
+                         std::vector<int> &pos, int *rec) {
+  const EmFamHost &F = H.fam[f];
+  const int n = F.n_nodes, *par = H.parent.data() + H.off_n[f];
+  const int x = mv[0], y = mv[1];
+  if (x < 0 || x >= n) return fail(CB_EINVAL, "%s: family %d move %d: x = %d (0 <= index < %d)", who, f, m, x, n);
+  if (y < 0 || y >= n) return fail(CB_EINVAL, "%s: family %d move %d: y = %d (0 <= index < %d)", who, f, m, y, n);
+  if (x == F.root) return fail(CB_EINVAL, "%s: family %d move %d: x = %d is the root", who, f, m, x);
+  const int p = par[x];
+  if (p == F.root) return fail(CB_EINVAL, "%s: family %d move %d: p = parent[x] = %d is the root", who, f, m, p);
+  const int np = F.child_ptr[p + 1] - F.child_ptr[p];
+  if (np != 2) return fail(CB_EINVAL, "%s: family %d move %d: p = parent[x] = %d has %d children (exactly 2)", who, f, m, p, np);
+  const int c0 = F.child_idx[F.child_ptr[p]], s = c0 != x ? c0 : F.child_idx[F.child_ptr[p] + 1], g = par[p];
+  if (y == F.root) return fail(CB_EINVAL, "%s: family %d move %d: y = %d is the root", who, f, m, y);
+  if (y == x) return fail(CB_EINVAL, "%s: family %d move %d: y = %d equals x", who, f, m, y);
+  if (y == p) return fail(CB_EINVAL, "%s: family %d move %d: y = %d equals p = parent[x]", who, f, m, y);
+  if (y == s) return fail(CB_EINVAL, "%s: family %d move %d: y = %d equals s, the other child of parent[x]", who, f, m, y);
+  static const char *names[3] = {"tau_s", "tau_p", "tau_y"};
+  for (int k = 0; k < 3; ++k)
+    if (mv[2 + k] < 0 || mv[2 + k] >= T)
+      return fail(CB_EINVAL, "%s: family %d move %d: %s = %d (0 <= index < %d)", who, f, m, names[k], mv[2 + k], T);
+  // y and its ancestors up to s, x or the root
+  std::vector<int> chain;
+  for (int w = y; w >= 0 && w != x; w = w == s ? -1 : par[w]) chain.push_back(w);
+  const int top = chain.back();
+  if (top != s && top != F.root) return fail(CB_EINVAL, "%s: family %d move %d: y = %d lies in the subtree of x = %d", who, f, m, y, x);
+  auto is_leaf = [&](int w) { return F.child_ptr[w] == F.child_ptr[w + 1]; };
+  auto step = [&](int i, int op, int t, int node, int ex1, int ex2, int flags) {
+    int *st = rec + SPR_HEAD + SPR_STEP * i;
+    st[0] = op, st[1] = t, st[2] = node, st[3] = ex1, st[4] = ex2, st[5] = flags;
+  };
+  std::fill(rec, rec + SPR_REC, 0);
+  int d = 0;
+  if (top == s) {   // below s: s = z0, ..., zd = y
+    d = (int)chain.size() - 1;
+    if (d > CB_SPR_MAX_RADIUS)
+      return fail(CB_EINVAL, "%s: family %d move %d: y = %d is at distance %d of x = %d (at most %d)", who, f, m, y, d, x, CB_SPR_MAX_RADIUS);
+    step(0, SPR_NONE, 0, g, p, -1, SPR_ADD_U);
+    for (int i = 1; i <= d; ++i) {
+      const int z = chain[d - i + 1];
+      step(i, SPR_DOWN, i == 1 ? mv[2] : tau[z], z, chain[d - i], -1, 0);
+    }
+    step(d + 1, 0, 0, y, -1, -1, is_leaf(y) ? SPR_LEAF : 0);
+  } else {          // through g: up k ancestors of g to the first that is y or above it, then down j nodes to y
+    for (size_t i = 0; i < chain.size(); ++i) pos[chain[i]] = (int)i;
+    std::vector<int> anc(1, g);
+    while (pos[anc.back()] < 0) anc.push_back(par[anc.back()]);
+    const int k = (int)anc.size() - 1, j = pos[anc.back()];
+    for (int w : chain) pos[w] = -1;
+    d = k + 1 + std::max(j - 1, 0);
+    if (d > CB_SPR_MAX_RADIUS)
+      return fail(CB_EINVAL, "%s: family %d move %d: y = %d is at distance %d of x = %d (at most %d)", who, f, m, y, d, x, CB_SPR_MAX_RADIUS);
+    const int z1 = j > 0 ? chain[j - 1] : -1;
+    step(0, SPR_NONE, 0, s, -1, -1, is_leaf(s) ? SPR_LEAF : 0);
+    for (int i = 1; i <= k + 1; ++i) {
+      const bool turn = i == k + 1 && j > 0;   // the outside of z1: U of the top and all it holds but z1
+      step(i, SPR_UP, i == 1 ? mv[2] : tau[anc[i - 2]], anc[i - 1], i == 1 ? p : anc[i - 2], turn ? z1 : -1, turn ? SPR_ADD_U : 0);
+    }
+    for (int i = 1; i < j; ++i) step(k + 1 + i, SPR_DOWN, tau[chain[j - i]], chain[j - i], chain[j - i - 1], -1, 0);
+    if (j == 0) step(d + 1, 1, 0, par[y], y, -1, SPR_ADD_U);
+    else step(d + 1, 0, 0, y, -1, -1, is_leaf(y) ? SPR_LEAF : 0);
+  }
+  rec[0] = d + 1, rec[1] = x, rec[2] = mv[3], rec[3] = mv[4];
+  return CB_OK;
+}
+
+constexpr size_t SPR_LL_BYTES = (size_t)256 << 20;   // ll'[move][unit] of one chunk of moves, at most (one move always goes); the
+                                                     // test hook CB_SPR_LL_BYTES: the results do not depend on the chunking
+
+extern "C" int cb_bl_spr_scan(cb_bl_s *h, const int *n_moves, const int *moves, double *delta, double *ll_moves, double *fam_ll,
+                              double *kernel_ms) {
+  static const char *who = "cb_bl_spr_scan";
+  if (!h) return fail(CB_EINVAL, "%s: NULL handle", who);
+  if (!n_moves || !delta) return fail(CB_EINVAL, "%s: NULL argument", who);
+  // every move, on the host, before any device work: its checks and its step record
+  const EmForestHost &H = h->forest.host;
+  const int n_fam = H.n_fam(), S = h->forest.S;
+  std::vector<size_t> off_m(n_fam + 1, 0), off_o(n_fam + 1, 0);
+  for (int f = 0; f < n_fam; ++f) {
+    if (n_moves[f] < 0) return fail(CB_EINVAL, "%s: family %d: n_moves = %d", who, f, n_moves[f]);
+    off_m[f + 1] = off_m[f] + n_moves[f];
+    off_o[f + 1] = off_o[f] + (size_t)n_moves[f] * H.fam[f].n_units;
+  }
+  if (off_m[n_fam] > 0 && !moves) return fail(CB_EINVAL, "%s: NULL argument", who);
+  size_t max_moves = 0, max_out = 0;
+  std::vector<int> chunk(n_fam, 0), pos;
+  std::vector<int> recs(off_m[n_fam] * SPR_REC);
+  const size_t bound = cb_hook_bytes("CB_SPR_LL_BYTES", SPR_LL_BYTES);
+  for (int f = 0; f < n_fam; ++f) {
+    const EmFamHost &F = H.fam[f];
+    pos.assign(F.n_nodes, -1);
+    for (int m = 0; m < n_moves[f]; ++m) {
+      const int rc_m = bl_spr_record(who, H, f, m, moves + 5 * (off_m[f] + m), h->tau.data() + H.off_n[f], h->T, pos,
+                                     recs.data() + (off_m[f] + m) * SPR_REC);
+      if (rc_m != CB_OK) return rc_m;
+    }
+    if (n_moves[f] == 0) continue;
+    const size_t n_blocks = ((size_t)F.n_units + 64 / S - 1) / (64 / S);
+    const size_t fit = std::min(bound / ((size_t)F.n_units * sizeof(double)), (size_t)INT32_MAX / n_blocks);
+    chunk[f] = (int)std::min<size_t>(n_moves[f], std::max<size_t>(fit, 1));
+    max_moves = std::max(max_moves, (size_t)n_moves[f]);
+    max_out = std::max(max_out, (size_t)chunk[f] * F.n_units);
+  }
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.0;
+  if (max_moves > 0) {
+    HIP_TRY(hipSetDevice(h->forest.device));
+    // the messages of the families that are scanned, at the current indices: after a round the resident ones are its start's
+    CbKernelTimer passes(kernel_ms != nullptr, h->ev[0], h->ev[1]);
+    int rc = passes.begin(false);
+    if (rc != CB_OK) return rc;
+    for (int f = 0; f < n_fam; ++f)
+      if (n_moves[f] > 0) bl_launch_passes(h, f, true);
+    HIP_TRY(hipGetLastError());
+    if ((rc = passes.end(kernel_ms)) != CB_OK) return rc;
+    std::vector<double> host_out(ll_moves ? max_out : 0);
+    CbDevBufs bufs;   // this call's: freed on every return path
+    int *drec = bufs.up<int>(nullptr, max_moves * SPR_REC, rc);
+    double *dout = bufs.up<double>(nullptr, max_out, rc), *ddelta = bufs.up<double>(nullptr, max_moves, rc);
+    if (rc != CB_OK) return rc;
+    for (int f = 0; f < n_fam; ++f) {
+      if (n_moves[f] == 0) continue;
+      const EmFamView w = h->forest.view(f);
+      const EmFamHost &F = w.F;
+      const int U = F.n_units;
+      HIP_TRY(hipMemcpy(drec, recs.data() + off_m[f] * SPR_REC, (size_t)n_moves[f] * SPR_REC * sizeof(int), hipMemcpyHostToDevice));
+      SprArgs a{};
+      a.S = S; a.n_units = U; a.n_cats = F.n_cats; a.root = F.root; a.n_blocks = w.n_blocks; a.bank_base = h->bank_base[f];
+      a.child_ptr = w.child_ptr; a.child_idx = w.child_idx; a.unit_cat = w.unit_cat; a.codes = w.codes; a.P = h->dP;
+      a.pi_root = h->dpi; a.msg = w.msg; a.U = w.U; a.out = dout;
+      NniArgs b{};      // nni_sum_kernel's fields
+      b.n_units = U; b.ll = w.ll; b.out = dout;
+      for (int m0 = 0; m0 < n_moves[f]; m0 += chunk[f]) {
+        const int nm = std::min(chunk[f], n_moves[f] - m0);
+        a.rec = drec + (size_t)m0 * SPR_REC;
+        b.delta = ddelta + m0;
+        CbKernelTimer scan(kernel_ms != nullptr, h->ev[0], h->ev[1]);
+        double ms = 0.0;
+        if ((rc = scan.begin(false)) != CB_OK) return rc;
+        hipLaunchKernelGGL(spr_scan_kernel, dim3((unsigned)nm * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
+        hipLaunchKernelGGL(nni_sum_kernel, dim3((unsigned)nm), dim3(64), 0, 0, b);
         HIP_TRY(hipGetLastError());
         if ((rc = scan.end(&ms)) != CB_OK) return rc;
         if (kernel_ms) kernel_ms[1] += ms;

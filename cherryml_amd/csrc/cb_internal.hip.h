@@ -99,7 +99,7 @@ int cb_tb_launch_ew(const CbTbEwArgs &a, hipStream_t stream, hipEvent_t stop, in
 //   eigensolver (train_host.hip.h, eigh_large_host.hip.h): CB_EIGH_HOST, CB_NO_HYBRID, CB_EIGH_SHORT_PLAN;
 //   counts (create_host.hip.h): CB_NO_SYM;   faults (cherrybank.hip, train_host.hip.h): CB_FAULT_INJECT;
 //   chunk bounds (cb_hook_bytes below) -- the site-rate scan's candidates (cb_sr.hip): CB_SR_MSG_BYTES; the NNI scan's moves
-//     (cb_bl.hip): CB_NNI_LL_BYTES; the ancestral reconstruction's nodes (cb_bl.hip): CB_ANC_POST_BYTES; the branch supports'
+//     (cb_bl.hip): CB_NNI_LL_BYTES; the SPR scan's moves (cb_bl.hip): CB_SPR_LL_BYTES; the ancestral reconstruction's nodes (cb_bl.hip): CB_ANC_POST_BYTES; the branch supports'
 //     groups of moves (cb_bl.hip): CB_SUP_BYTES; the search bootstrap's move tiles (cb_bl.hip): CB_UFB_BYTES; neighbour joining's resident matrices (cb_nj.hip): CB_NJ_BYTES; the bootstrap's (cb_boot.hip): CB_BOOT_BYTES;
 //     the transfer distances' resident leaf sets (cb_transfer.hip): CB_TBE_BYTES.
 // (CB_DEBUG and CB_TRACE_SLOW only log; CB_BANK_STREAMS is a documented opt-in.)

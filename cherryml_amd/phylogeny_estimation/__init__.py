@@ -15,7 +15,9 @@ of sequences and the joins on the GPU (`bootstrap_nj_records`, `bootstrap_suppor
 every replicate by xor and popcount on the GPU (`transfer_distances`, `transfer_bootstrap_supports`, the stage
 `nj_transfer_supports`); bootstrap supports from the NNI search's own trees, the best resampled candidate of every replicate kept
 on the GPU while the search runs (`BranchLengthFitter.bootstrap_best`, `ufboot_supports`, the `output_bootstrap_dir` of
-`ml_nni_trees` / `nj_nni_trees`)."""
+`ml_nni_trees` / `nj_nni_trees`); topology search by subtree prune-and-regraft scored on the GPU from the same resident messages
+(`BranchLengthFitter.spr_scan`, `enumerate_spr_moves`, `spr_indices`, `select_spr`, `apply_spr`, the stages `ml_spr_trees` and
+`nj_spr_trees`)."""
 from ._ble import (  # noqa: F401
     BleBank,
     branch_lengths,
@@ -40,6 +42,7 @@ from ._nj import neighbor_joining_device, neighbor_joining_device_batch, nj_join
 from ._ml_lengths import BranchLengthFitter, ml_branch_lengths, nj_ml_trees  # noqa: F401,E402
 from ._site_rates import ml_lengths_and_site_rates, ml_site_rates, nj_ml_rates_trees, tree_site_rates  # noqa: F401,E402
 from ._nni import apply_nni, enumerate_nni_moves, ml_nni_trees, nj_nni_trees, select_nni  # noqa: F401,E402
+from ._spr import apply_spr, enumerate_spr_moves, ml_spr_trees, nj_spr_trees, select_spr, spr_indices  # noqa: F401,E402
 from ._ancestral import ml_ancestral_sequences  # noqa: F401,E402
 from ._supports import ml_branch_supports, read_supports, write_supports  # noqa: F401,E402
 from ._bootstrap import (  # noqa: F401,E402

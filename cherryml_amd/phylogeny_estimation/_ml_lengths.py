@@ -59,6 +59,7 @@ class BranchLengthFitter(_lib.ResidentHandle):
         self.last_kernel_ms = (0.0, 0.0)   # (passes, M-step) of the last round
         self._parent = np.split(self._args[0], np.cumsum(self.n_nodes)[:-1])
         self.last_nni_kernel_ms = (0.0, 0.0)   # (passes, scan) of the last nni_scan
+        self.last_spr_kernel_ms = (0.0, 0.0)   # (passes, scan) of the last spr_scan
         self.last_ancestral_kernel_ms = (0.0, 0.0)   # (passes, reconstruction) of the last ancestral_states
         self.last_support_kernel_ms = (0.0, 0.0, 0.0)   # (passes, scan, resampling) of the last branch_supports
         self.last_ufboot_kernel_ms = (0.0, 0.0, 0.0)   # (passes, scan, resampling and reduction) of the last bootstrap_best
@@ -134,6 +135,40 @@ class BranchLengthFitter(_lib.ResidentHandle):
             raise _lib.CherryBankError(f"cb_bl_nni_scan failed ({rc}): {_lib.load().cb_last_error().decode('utf-8', 'replace')}")
         _lib.check(rc, "cb_bl_nni_scan")
         self.last_nni_kernel_ms = (ms[0], ms[1])
+        deltas = np.split(delta, np.cumsum(n_moves)[:-1])
+        if not per_site:
+            return moves, deltas
+        lls = [x.reshape(int(k), int(u)) for x, k, u in zip(np.split(ll, np.cumsum(sizes)[:-1]), n_moves, self.n_units)]
+        return moves, deltas, lls
+
+    def spr_moves(self, radius: int = 3) -> List[np.ndarray]:
+        """per family the int32 [n, 5] array of ALL subtree prune-and-regraft moves (x, y, tau_s, tau_p, tau_y) of its tree within
+        `radius`, at the handle's current indices: (x, y) from `_spr.enumerate_spr_moves` (x ascending, then y), the three
+        indices from `_spr.spr_indices`"""
+        from ._spr import _moves_at
+        return [_moves_at(p, tau, self.grid, radius) for p, tau in zip(self._parent, self.indices())]
+
+    def spr_scan(self, moves: Optional[Sequence] = None, radius: int = 3, per_site: bool = False):
+        """Score subtree prune-and-regraft moves by likelihood at the current indices (`cb_bl_spr_scan`: one launch per family
+        from the resident messages) -> (moves, delta) and with `per_site` also ll_moves: per family the [n, 5] moves
+        (`spr_moves(radius)` when None; a family with none is skipped), delta [n] = the log-likelihood of the rearranged tree
+        at the move's three indices minus the present one, and ll_moves [n, n_sites] the rearranged tree's log-likelihood per
+        site.  Changes nothing any other method returns.  Sets `last_spr_kernel_ms` = (passes, scan)."""
+        moves = self.spr_moves(radius) if moves is None else [np.ascontiguousarray(m, dtype=np.int32).reshape(-1, 5) for m in moves]
+        if len(moves) != self.n_nodes.size:
+            raise ValueError(f"spr_scan: {len(moves)} move lists for {self.n_nodes.size} families")
+        n_moves = np.array([len(m) for m in moves], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(moves).reshape(-1), dtype=np.int32)
+        delta = np.empty(int(n_moves.sum()))
+        sizes = n_moves.astype(np.int64) * self.n_units
+        ll = np.empty(int(sizes.sum())) if per_site else None
+        ms = (ctypes.c_double * 2)(0.0, 0.0)
+        rc = _lib.load().cb_bl_spr_scan(self._handle(), n_moves.ctypes.data, flat.ctypes.data, delta.ctypes.data,
+                                        ll.ctypes.data if per_site else None, None, ctypes.addressof(ms))
+        if rc == _lib.CB_EINVAL:   # a refused move list: the library's message names family, move and value
+            raise _lib.CherryBankError(f"cb_bl_spr_scan failed ({rc}): {_lib.load().cb_last_error().decode('utf-8', 'replace')}")
+        _lib.check(rc, "cb_bl_spr_scan")
+        self.last_spr_kernel_ms = (ms[0], ms[1])
         deltas = np.split(delta, np.cumsum(n_moves)[:-1])
         if not per_site:
             return moves, deltas

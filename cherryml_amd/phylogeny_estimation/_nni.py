@@ -8,7 +8,7 @@ passes leave resident; `select_nni` picks a set of moves at disjoint places, `ap
 `ml_nni_trees` alternates the branch-length EM with scan / select / apply, keeping a candidate tree only if its likelihood at
 the same lengths is strictly higher.  `nj_nni_trees` is the tree estimator `nj_trees` + `ml_nni_trees`.
 
-Out of scope: SPR / TBR moves, changing a handle's topology in place (a rearranged tree gets a new handle), refitting site
+Out of scope: SPR / TBR moves (SPR is `_spr.py`), changing a handle's topology in place (a rearranged tree gets a new handle), refitting site
 rates inside the search, S > 32."""
 import os
 import time

@@ -730,8 +730,26 @@ int cb_em_destroy(cb_em h);
  *   delta_rep -- k from unit 0 up in steps of 4, zero operands past the ends -- so Delta_m^r is bitwise its delta_rep, and a tie
  *   goes to the lowest code: the result does not depend on how moves, replicates or families are tiled, sliced or chunked.  A
  *   family with no moves gets B^r against the incoming best.  No atomics.  The call changes nothing cb_bl_round, cb_bl_get,
- *   cb_bl_nni_scan, cb_bl_supports or cb_bl_ancestral return; its device buffers are its own, freed before it returns. */
+ *   cb_bl_nni_scan, cb_bl_supports or cb_bl_ancestral return; its device buffers are its own, freed before it returns.
+ *
+ * cb_bl_spr_scan: subtree prune-and-regraft moves of the handle's trees, scored by likelihood at the CURRENT indices (DESIGN.md
+ *   section 25).  A move of family f is (x, y, tau_s, tau_p, tau_y): x the pruned node, p = parent[x] neither the root nor other
+ *   than binary, s the other child of p, g = parent[p]; y the node whose edge receives the subtree -- not the root, not x, p or
+ *   s, not in the subtree of x.  The rearranged tree has parent[s] = g, parent[p] = the old parent[y], parent[y] = p, and x stays
+ *   under p; the edges above s, p and y take the grid indices tau_s, tau_p and tau_y (any three in [0, T)), every other node
+ *   keeps its index.  With T' the tree without x and p (s under g), the distance of y is the number of nodes of T' on the path
+ *   between the merged edge g-s and the edge above y; it is at most CB_SPR_MAX_RADIUS (the step record of a move is a fixed
+ *   block of the call's device buffer; 8 covers every search radius in use).  Distance 1 gives the NNI topologies.  n_moves
+ *   [n_fam] (0: the family is skipped, no pass runs for it), moves [sum n_moves][5].  Every move is validated on the host before
+ *   any device work (CB_EINVAL names family, move and value: x or y out of range, x the root, p the root, p not binary, y the
+ *   root, x, p or s, y below x, a distance above CB_SPR_MAX_RADIUS, a tau outside [0, T), a negative count).  The call runs the
+ *   passes of the scanned families at the current indices, then one launch per family (per chunk of its moves, under a fixed
+ *   byte bound on ll') forms for every move and site the exact log-likelihood of the rearranged tree: distance + 2 products of
+ *   size S x S, along the way from the prune point to y and through the two new edges.  delta, ll_moves, fam_ll and kernel_ms
+ *   are cb_bl_nni_scan's.  The call changes nothing any other cb_bl_* call returns; ll' and the moves' records live in buffers
+ *   of the call, freed before it returns; no atomics: a move's results do not depend on the other moves, chunks or families. */
 #define CB_BL_MAX_CATS 64
+#define CB_SPR_MAX_RADIUS 8
 typedef struct cb_bl_s *cb_bl;
 int cb_bl_create(int device, int S, int T, const double *grid, const double *Q, const double *pi_root, int n_fam,
                  const int *n_nodes, const int *parent, const double *length, const int *n_units, const double *unit_rate,
@@ -739,6 +757,8 @@ int cb_bl_create(int device, int S, int T, const double *grid, const double *Q, 
 int cb_bl_round(cb_bl h, int *n_changed, double *fam_ll, double *kernel_ms);
 int cb_bl_get(cb_bl h, int *index, double *ll, double *fam_ll);
 int cb_bl_nni_scan(cb_bl h, const int *n_moves, const int *moves, double *delta, double *ll_moves, double *fam_ll,
+                   double *kernel_ms);
+int cb_bl_spr_scan(cb_bl h, const int *n_moves, const int *moves, double *delta, double *ll_moves, double *fam_ll,
                    double *kernel_ms);
 int cb_bl_ancestral(cb_bl h, int8_t *state, double *conf, double *post, double *fam_ll, double *kernel_ms);
 int cb_bl_supports(cb_bl h, int n_rep, const uint64_t *seeds, const int *n_moves, const int *moves, double *alrt, int *sh_count,
