@@ -4,6 +4,11 @@
 // scan's per-site log-likelihoods (sup.hip.h; cb_bl_supports) and the best resampled candidate per bootstrap replicate among a
 // tree and its NNI neighbours (ufb.hip.h; cb_bl_bootstrap_best) and the subtree prune-and-regraft scan on the same messages
 // (spr.hip.h; cb_bl_spr_scan).
+// The five calls on the resident messages are built from the same steps, each in one place: the move lists (bl_move_lists, and
+// bl_check_moves / bl_spr_record per move), the passes at the current indices (bl_refresh), a timed group of launches (bl_timed),
+// the arguments of the scan and of the resampling weights (bl_nni_args, bl_weight_args) and the l_u the passes leave
+// (bl_finish).  The two scans share their driver, bl_scan; the supports, the bootstrap and the reconstruction keep their own
+// chunking rules and their own middle.
 #include "cb_internal.hip.h"
 #include "common.hip.h"
 #include "bl.hip.h"
@@ -241,32 +246,111 @@ static int bl_check_moves(const char *who, const EmForestHost &H, int f, int n_m
   return CB_OK;
 }
 
-constexpr size_t NNI_LL_BYTES = (size_t)256 << 20;   // ll'[move][unit] of one chunk of moves, at most (one move always goes); the
-                                                     // test hook CB_NNI_LL_BYTES: the results do not depend on the chunking
+// ---- the steps that the calls on the resident messages share (the scans, the supports, the bootstrap, the reconstruction) ----
 
-extern "C" int cb_bl_nni_scan(cb_bl_s *h, const int *n_moves, const int *moves, double *delta, double *ll_moves, double *fam_ll,
-                              double *kernel_ms) {
-  static const char *who = "cb_bl_nni_scan";
-  if (!h) return fail(CB_EINVAL, "%s: NULL handle", who);
-  if (!n_moves || !delta) return fail(CB_EINVAL, "%s: NULL argument", who);
-  // every triple, on the host, before any device work
-  const EmForestHost &H = h->forest.host;
-  const int n_fam = H.n_fam(), S = h->forest.S;
-  std::vector<size_t> off_m(n_fam + 1, 0), off_o(n_fam + 1, 0);
+// The move lists of a call: refuses a negative count and, where there is a move, NULL `moves`.  off_m: per family its first
+// move (and the total); has: per family whether it has a move.
+static int bl_move_lists(const char *who, const EmForestHost &H, const int *n_moves, const int *moves, std::vector<size_t> &off_m,
+                         std::vector<char> &has) {
+  const int n_fam = H.n_fam();
+  off_m.assign(n_fam + 1, 0);
+  has.assign(n_fam, 0);
   for (int f = 0; f < n_fam; ++f) {
     if (n_moves[f] < 0) return fail(CB_EINVAL, "%s: family %d: n_moves = %d", who, f, n_moves[f]);
     off_m[f + 1] = off_m[f] + n_moves[f];
-    off_o[f + 1] = off_o[f] + (size_t)n_moves[f] * H.fam[f].n_units;
+    has[f] = n_moves[f] > 0;
   }
   if (off_m[n_fam] > 0 && !moves) return fail(CB_EINVAL, "%s: NULL argument", who);
+  return CB_OK;
+}
+
+// The kernels `launch(timer)` enqueues, under the handle's events: their time is added to kernel_ms[slot] and, where launch
+// calls timer.lap(), the time of what follows the lap to kernel_ms[slot + 1].  kernel_ms NULL: no event and no wait.
+template <typename Launch>
+static int bl_timed(cb_bl_s *h, double *kernel_ms, int slot, Launch &&launch) {
+  CbKernelTimer timer(kernel_ms != nullptr, h->ev[0], h->ev[2], h->ev[1]);
+  double ms[2] = {0.0, 0.0};
+  int rc = timer.begin(false);
+  if (rc != CB_OK) return rc;
+  if ((rc = launch(timer)) != CB_OK) return rc;
+  HIP_TRY(hipGetLastError());
+  if ((rc = timer.end(ms)) != CB_OK) return rc;
+  if (kernel_ms) kernel_ms[slot] += ms[0];
+  if (timer.lapped) kernel_ms[slot + 1] += ms[1];   // (lapped: only with kernel_ms)
+  return CB_OK;
+}
+
+// The messages and l_u of the families in `which` at the current indices, their time in kernel_ms[0] (zeroed by the caller):
+// after a round the resident ones are its start's.
+static int bl_refresh(cb_bl_s *h, const std::vector<char> &which, double *kernel_ms) {
+  HIP_TRY(hipSetDevice(h->forest.device));
+  return bl_timed(h, kernel_ms, 0, [&](CbKernelTimer &) -> int {
+    for (size_t f = 0; f < which.size(); ++f)
+      if (which[f]) bl_launch_passes(h, (int)f, true);
+    return CB_OK;
+  });
+}
+
+// After bl_refresh(which) and the call's own kernels: dll of those families holds l_u at the current indices -- the bits
+// cb_bl_get's inside pass would write -- so the stale ones among them get their sums and are fresh.  fam_ll (or NULL) takes
+// every family's sum, NaN for one that is still not fresh.
+static int bl_finish(cb_bl_s *h, const std::vector<char> &which, double *fam_ll) {
+  const int n_fam = h->forest.host.n_fam();
+  std::vector<char> stale(n_fam);
+  bool any = false;
+  for (int f = 0; f < n_fam; ++f) {
+    stale[f] = which[f] && !h->ll_fresh[f];
+    any = any || which[f];
+  }
+  if (any) {
+    const int rc = bl_read_ll(h, stale, nullptr);
+    if (rc != CB_OK) return rc;
+    for (int f = 0; f < n_fam; ++f)
+      if (stale[f]) h->ll_fresh[f] = 1;
+  }
+  if (fam_ll)
+    for (int f = 0; f < n_fam; ++f) fam_ll[f] = h->ll_fresh[f] ? h->fam_ll[f] : std::nan("");
+  return CB_OK;
+}
+
+// nni_scan_kernel's and nni_sum_kernel's arguments for a family, but the chunk's moves and delta
+static NniArgs bl_nni_args(const cb_bl_s *h, const EmFamView &w, double *out) {
+  NniArgs a{};
+  a.S = h->forest.S; a.n_units = w.F.n_units; a.n_cats = w.F.n_cats; a.root = w.F.root; a.n_blocks = w.n_blocks;
+  a.parent = w.parent; a.child_ptr = w.child_ptr; a.child_idx = w.child_idx; a.qb = w.qb; a.unit_cat = w.unit_cat; a.P = h->dP;
+  a.pi_root = h->dpi; a.msg = w.msg; a.U = w.U; a.ll = w.ll; a.out = out;
+  return a;
+}
+
+// sup_weights_kernel's arguments for a family: its inverse permutation, uploaded to dinv (inv: host room for it), and its seed
+static int bl_weight_args(const EmFamHost &F, uint64_t seed, std::vector<int> &inv, int *dinv, double *dW, SupWeightArgs &wa) {
+  for (int k = 0; k < F.n_units; ++k) inv[F.perm[k]] = k;
+  HIP_TRY(hipMemcpy(dinv, inv.data(), (size_t)F.n_units * sizeof(int), hipMemcpyHostToDevice));
+  wa = SupWeightArgs{};
+  wa.n_units = F.n_units; wa.k0 = (uint32_t)(seed & 0xFFFFFFFFu); wa.k1 = (uint32_t)(seed >> 32); wa.inv = dinv; wa.W = dW;
+  return CB_OK;
+}
+
+constexpr size_t SCAN_LL_BYTES = (size_t)256 << 20;   // ll'[move][unit] of one chunk of moves, at most (one move always goes); the
+                                                      // test hooks CB_NNI_LL_BYTES and CB_SPR_LL_BYTES: the results do not
+                                                      // depend on the chunking
+
+// The driver of cb_bl_nni_scan and cb_bl_spr_scan, after their checks.  hook: the name of the byte bound's test hook; rows:
+// per move (off_m) `width` ints, what the scan kernel reads of it; launch(f, w, drows, dout, ddelta, nm): enqueues the scan
+// kernel and nni_sum_kernel for nm moves of family f with view w, whose rows, ll' and deltas start at the three device pointers.
+template <typename Launch>
+static int bl_scan(cb_bl_s *h, const char *hook, const int *n_moves, const std::vector<size_t> &off_m, const std::vector<char> &has,
+                   const int *rows, size_t width, Launch &&launch, double *delta, double *ll_moves, double *fam_ll,
+                   double *kernel_ms) {
+  const EmForestHost &H = h->forest.host;
+  const int n_fam = H.n_fam(), S = h->forest.S;
+  // moves per launch: all of a family's, fewer under the byte bound and where moves x site tiles would pass 2^31
   size_t max_moves = 0, max_out = 0;
   std::vector<int> chunk(n_fam, 0);
-  const size_t bound = cb_hook_bytes("CB_NNI_LL_BYTES", NNI_LL_BYTES);
+  const size_t bound = cb_hook_bytes(hook, SCAN_LL_BYTES);
   for (int f = 0; f < n_fam; ++f) {
+    if (!has[f]) continue;
     const EmFamHost &F = H.fam[f];
-    const int rc_f = bl_check_moves(who, H, f, n_moves[f], moves + 3 * off_m[f]);
-    if (rc_f != CB_OK) return rc_f;
-    if (n_moves[f] == 0) continue;
     const size_t n_blocks = ((size_t)F.n_units + 64 / S - 1) / (64 / S);
     const size_t fit = std::min(bound / ((size_t)F.n_units * sizeof(double)), (size_t)INT32_MAX / n_blocks);
     chunk[f] = (int)std::min<size_t>(n_moves[f], std::max<size_t>(fit, 1));
@@ -275,62 +359,59 @@ extern "C" int cb_bl_nni_scan(cb_bl_s *h, const int *n_moves, const int *moves, 
   }
   if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.0;
   if (max_moves > 0) {
-    HIP_TRY(hipSetDevice(h->forest.device));
-    // the messages of the families that are scanned, at the current indices: after a round the resident ones are its start's
-    CbKernelTimer passes(kernel_ms != nullptr, h->ev[0], h->ev[1]);
-    int rc = passes.begin(false);
+    int rc = bl_refresh(h, has, kernel_ms);
     if (rc != CB_OK) return rc;
-    for (int f = 0; f < n_fam; ++f)
-      if (n_moves[f] > 0) bl_launch_passes(h, f, true);
-    HIP_TRY(hipGetLastError());
-    if ((rc = passes.end(kernel_ms)) != CB_OK) return rc;
     std::vector<double> host_out(ll_moves ? max_out : 0);
     CbDevBufs bufs;   // this call's: freed on every return path
-    int *dmoves = bufs.up<int>(nullptr, 3 * max_moves, rc);
+    int *drows = bufs.up<int>(nullptr, width * max_moves, rc);
     double *dout = bufs.up<double>(nullptr, max_out, rc), *ddelta = bufs.up<double>(nullptr, max_moves, rc);
     if (rc != CB_OK) return rc;
+    size_t off_o = 0;   // the family's first ll' in ll_moves
     for (int f = 0; f < n_fam; ++f) {
-      if (n_moves[f] == 0) continue;
+      if (!has[f]) continue;
       const EmFamView w = h->forest.view(f);
-      const EmFamHost &F = w.F;
-      const int U = F.n_units;
-      HIP_TRY(hipMemcpy(dmoves, moves + 3 * off_m[f], 3 * (size_t)n_moves[f] * sizeof(int), hipMemcpyHostToDevice));
-      NniArgs a{};
-      a.S = S; a.n_units = U; a.n_cats = F.n_cats; a.root = F.root; a.n_blocks = w.n_blocks;
-      a.parent = w.parent; a.child_ptr = w.child_ptr; a.child_idx = w.child_idx; a.qb = w.qb; a.unit_cat = w.unit_cat; a.P = h->dP;
-      a.pi_root = h->dpi; a.msg = w.msg; a.U = w.U; a.ll = w.ll; a.out = dout;
+      const int U = w.F.n_units;
+      HIP_TRY(hipMemcpy(drows, rows + width * off_m[f], width * n_moves[f] * sizeof(int), hipMemcpyHostToDevice));
       for (int m0 = 0; m0 < n_moves[f]; m0 += chunk[f]) {
         const int nm = std::min(chunk[f], n_moves[f] - m0);
-        a.moves = dmoves + 3 * (size_t)m0;
-        a.delta = ddelta + m0;
-        CbKernelTimer scan(kernel_ms != nullptr, h->ev[0], h->ev[1]);
-        double ms = 0.0;
-        if ((rc = scan.begin(false)) != CB_OK) return rc;
-        hipLaunchKernelGGL(nni_scan_kernel, dim3((unsigned)nm * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
-        hipLaunchKernelGGL(nni_sum_kernel, dim3((unsigned)nm), dim3(64), 0, 0, a);
-        HIP_TRY(hipGetLastError());
-        if ((rc = scan.end(&ms)) != CB_OK) return rc;
-        if (kernel_ms) kernel_ms[1] += ms;
+        rc = bl_timed(h, kernel_ms, 1, [&](CbKernelTimer &) -> int {
+          launch(f, w, drows + width * m0, dout, ddelta + m0, nm);
+          return CB_OK;
+        });
+        if (rc != CB_OK) return rc;
         // (the next chunk writes the same buffer: stream order puts it behind this chunk's sum)
         if (ll_moves) {   // device (category) order -> the caller's unit order
           HIP_TRY(hipMemcpy(host_out.data(), dout, (size_t)nm * U * sizeof(double), hipMemcpyDeviceToHost));
-          double *dst = ll_moves + off_o[f] + (size_t)m0 * U;
-          for (int m = 0; m < nm; ++m) em_unpermute(F.perm, host_out.data() + (size_t)m * U, dst + (size_t)m * U);
+          double *dst = ll_moves + off_o + (size_t)m0 * U;
+          for (int m = 0; m < nm; ++m) em_unpermute(w.F.perm, host_out.data() + (size_t)m * U, dst + (size_t)m * U);
         }
       }
       HIP_TRY(hipMemcpy(delta + off_m[f], ddelta, (size_t)n_moves[f] * sizeof(double), hipMemcpyDeviceToHost));
+      off_o += (size_t)n_moves[f] * U;
     }
-    // dll of the scanned families now holds l_u at the current indices -- the bits cb_bl_get's inside pass would write
-    std::vector<char> stale(n_fam);
-    for (int f = 0; f < n_fam; ++f) stale[f] = n_moves[f] > 0 && !h->ll_fresh[f];
-    rc = bl_read_ll(h, stale, nullptr);
-    if (rc != CB_OK) return rc;
-    for (int f = 0; f < n_fam; ++f)
-      if (stale[f]) h->ll_fresh[f] = 1;
   }
-  if (fam_ll)
-    for (int f = 0; f < n_fam; ++f) fam_ll[f] = h->ll_fresh[f] ? h->fam_ll[f] : std::nan("");
-  return CB_OK;
+  return bl_finish(h, has, fam_ll);
+}
+
+extern "C" int cb_bl_nni_scan(cb_bl_s *h, const int *n_moves, const int *moves, double *delta, double *ll_moves, double *fam_ll,
+                              double *kernel_ms) {
+  static const char *who = "cb_bl_nni_scan";
+  if (!h) return fail(CB_EINVAL, "%s: NULL handle", who);
+  if (!n_moves || !delta) return fail(CB_EINVAL, "%s: NULL argument", who);
+  // every triple, on the host, before any device work
+  const EmForestHost &H = h->forest.host;
+  std::vector<size_t> off_m;
+  std::vector<char> has;
+  int rc = bl_move_lists(who, H, n_moves, moves, off_m, has);
+  for (int f = 0; f < H.n_fam() && rc == CB_OK; ++f) rc = bl_check_moves(who, H, f, n_moves[f], moves + 3 * off_m[f]);
+  if (rc != CB_OK) return rc;
+  auto launch = [h](int, const EmFamView &w, const int *dmoves, double *dout, double *ddelta, int nm) {
+    NniArgs a = bl_nni_args(h, w, dout);
+    a.moves = dmoves; a.delta = ddelta;
+    hipLaunchKernelGGL(nni_scan_kernel, dim3((unsigned)nm * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
+    hipLaunchKernelGGL(nni_sum_kernel, dim3((unsigned)nm), dim3(64), 0, 0, a);
+  };
+  return bl_scan(h, "CB_NNI_LL_BYTES", n_moves, off_m, has, moves, 3, launch, delta, ll_moves, fam_ll, kernel_ms);
 }
 
 // Move m of family f, (x, y, tau_s, tau_p, tau_y), on the host: what cb_bl_spr_scan refuses, and the move's step record for
@@ -401,9 +482,6 @@ static int bl_spr_record(const char *who, const EmForestHost &H, int f, int m, c
   return CB_OK;
 }
 
-constexpr size_t SPR_LL_BYTES = (size_t)256 << 20;   // ll'[move][unit] of one chunk of moves, at most (one move always goes); the
-                                                     // test hook CB_SPR_LL_BYTES: the results do not depend on the chunking
-
 extern "C" int cb_bl_spr_scan(cb_bl_s *h, const int *n_moves, const int *moves, double *delta, double *ll_moves, double *fam_ll,
                               double *kernel_ms) {
   static const char *who = "cb_bl_spr_scan";
@@ -411,93 +489,31 @@ extern "C" int cb_bl_spr_scan(cb_bl_s *h, const int *n_moves, const int *moves, 
   if (!n_moves || !delta) return fail(CB_EINVAL, "%s: NULL argument", who);
   // every move, on the host, before any device work: its checks and its step record
   const EmForestHost &H = h->forest.host;
-  const int n_fam = H.n_fam(), S = h->forest.S;
-  std::vector<size_t> off_m(n_fam + 1, 0), off_o(n_fam + 1, 0);
-  for (int f = 0; f < n_fam; ++f) {
-    if (n_moves[f] < 0) return fail(CB_EINVAL, "%s: family %d: n_moves = %d", who, f, n_moves[f]);
-    off_m[f + 1] = off_m[f] + n_moves[f];
-    off_o[f + 1] = off_o[f] + (size_t)n_moves[f] * H.fam[f].n_units;
-  }
-  if (off_m[n_fam] > 0 && !moves) return fail(CB_EINVAL, "%s: NULL argument", who);
-  size_t max_moves = 0, max_out = 0;
-  std::vector<int> chunk(n_fam, 0), pos;
-  std::vector<int> recs(off_m[n_fam] * SPR_REC);
-  const size_t bound = cb_hook_bytes("CB_SPR_LL_BYTES", SPR_LL_BYTES);
-  for (int f = 0; f < n_fam; ++f) {
-    const EmFamHost &F = H.fam[f];
-    pos.assign(F.n_nodes, -1);
+  std::vector<size_t> off_m;
+  std::vector<char> has;
+  int rc = bl_move_lists(who, H, n_moves, moves, off_m, has);
+  if (rc != CB_OK) return rc;
+  std::vector<int> pos, recs(off_m.back() * SPR_REC);
+  for (int f = 0; f < H.n_fam(); ++f) {
+    pos.assign(H.fam[f].n_nodes, -1);
     for (int m = 0; m < n_moves[f]; ++m) {
-      const int rc_m = bl_spr_record(who, H, f, m, moves + 5 * (off_m[f] + m), h->tau.data() + H.off_n[f], h->T, pos,
-                                     recs.data() + (off_m[f] + m) * SPR_REC);
-      if (rc_m != CB_OK) return rc_m;
+      rc = bl_spr_record(who, H, f, m, moves + 5 * (off_m[f] + m), h->tau.data() + H.off_n[f], h->T, pos,
+                         recs.data() + (off_m[f] + m) * SPR_REC);
+      if (rc != CB_OK) return rc;
     }
-    if (n_moves[f] == 0) continue;
-    const size_t n_blocks = ((size_t)F.n_units + 64 / S - 1) / (64 / S);
-    const size_t fit = std::min(bound / ((size_t)F.n_units * sizeof(double)), (size_t)INT32_MAX / n_blocks);
-    chunk[f] = (int)std::min<size_t>(n_moves[f], std::max<size_t>(fit, 1));
-    max_moves = std::max(max_moves, (size_t)n_moves[f]);
-    max_out = std::max(max_out, (size_t)chunk[f] * F.n_units);
   }
-  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.0;
-  if (max_moves > 0) {
-    HIP_TRY(hipSetDevice(h->forest.device));
-    // the messages of the families that are scanned, at the current indices: after a round the resident ones are its start's
-    CbKernelTimer passes(kernel_ms != nullptr, h->ev[0], h->ev[1]);
-    int rc = passes.begin(false);
-    if (rc != CB_OK) return rc;
-    for (int f = 0; f < n_fam; ++f)
-      if (n_moves[f] > 0) bl_launch_passes(h, f, true);
-    HIP_TRY(hipGetLastError());
-    if ((rc = passes.end(kernel_ms)) != CB_OK) return rc;
-    std::vector<double> host_out(ll_moves ? max_out : 0);
-    CbDevBufs bufs;   // this call's: freed on every return path
-    int *drec = bufs.up<int>(nullptr, max_moves * SPR_REC, rc);
-    double *dout = bufs.up<double>(nullptr, max_out, rc), *ddelta = bufs.up<double>(nullptr, max_moves, rc);
-    if (rc != CB_OK) return rc;
-    for (int f = 0; f < n_fam; ++f) {
-      if (n_moves[f] == 0) continue;
-      const EmFamView w = h->forest.view(f);
-      const EmFamHost &F = w.F;
-      const int U = F.n_units;
-      HIP_TRY(hipMemcpy(drec, recs.data() + off_m[f] * SPR_REC, (size_t)n_moves[f] * SPR_REC * sizeof(int), hipMemcpyHostToDevice));
-      SprArgs a{};
-      a.S = S; a.n_units = U; a.n_cats = F.n_cats; a.root = F.root; a.n_blocks = w.n_blocks; a.bank_base = h->bank_base[f];
-      a.child_ptr = w.child_ptr; a.child_idx = w.child_idx; a.unit_cat = w.unit_cat; a.codes = w.codes; a.P = h->dP;
-      a.pi_root = h->dpi; a.msg = w.msg; a.U = w.U; a.out = dout;
-      NniArgs b{};      // nni_sum_kernel's fields
-      b.n_units = U; b.ll = w.ll; b.out = dout;
-      for (int m0 = 0; m0 < n_moves[f]; m0 += chunk[f]) {
-        const int nm = std::min(chunk[f], n_moves[f] - m0);
-        a.rec = drec + (size_t)m0 * SPR_REC;
-        b.delta = ddelta + m0;
-        CbKernelTimer scan(kernel_ms != nullptr, h->ev[0], h->ev[1]);
-        double ms = 0.0;
-        if ((rc = scan.begin(false)) != CB_OK) return rc;
-        hipLaunchKernelGGL(spr_scan_kernel, dim3((unsigned)nm * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
-        hipLaunchKernelGGL(nni_sum_kernel, dim3((unsigned)nm), dim3(64), 0, 0, b);
-        HIP_TRY(hipGetLastError());
-        if ((rc = scan.end(&ms)) != CB_OK) return rc;
-        if (kernel_ms) kernel_ms[1] += ms;
-        // (the next chunk writes the same buffer: stream order puts it behind this chunk's sum)
-        if (ll_moves) {   // device (category) order -> the caller's unit order
-          HIP_TRY(hipMemcpy(host_out.data(), dout, (size_t)nm * U * sizeof(double), hipMemcpyDeviceToHost));
-          double *dst = ll_moves + off_o[f] + (size_t)m0 * U;
-          for (int m = 0; m < nm; ++m) em_unpermute(F.perm, host_out.data() + (size_t)m * U, dst + (size_t)m * U);
-        }
-      }
-      HIP_TRY(hipMemcpy(delta + off_m[f], ddelta, (size_t)n_moves[f] * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    // dll of the scanned families now holds l_u at the current indices -- the bits cb_bl_get's inside pass would write
-    std::vector<char> stale(n_fam);
-    for (int f = 0; f < n_fam; ++f) stale[f] = n_moves[f] > 0 && !h->ll_fresh[f];
-    rc = bl_read_ll(h, stale, nullptr);
-    if (rc != CB_OK) return rc;
-    for (int f = 0; f < n_fam; ++f)
-      if (stale[f]) h->ll_fresh[f] = 1;
-  }
-  if (fam_ll)
-    for (int f = 0; f < n_fam; ++f) fam_ll[f] = h->ll_fresh[f] ? h->fam_ll[f] : std::nan("");
-  return CB_OK;
+  auto launch = [h](int f, const EmFamView &w, const int *drec, double *dout, double *ddelta, int nm) {
+    const EmFamHost &F = w.F;
+    SprArgs a{};
+    a.S = h->forest.S; a.n_units = F.n_units; a.n_cats = F.n_cats; a.root = F.root; a.n_blocks = w.n_blocks; a.bank_base = h->bank_base[f];
+    a.child_ptr = w.child_ptr; a.child_idx = w.child_idx; a.unit_cat = w.unit_cat; a.codes = w.codes; a.P = h->dP;
+    a.pi_root = h->dpi; a.msg = w.msg; a.U = w.U; a.out = dout; a.rec = drec;
+    NniArgs b{};      // nni_sum_kernel's fields
+    b.n_units = F.n_units; b.ll = w.ll; b.out = dout; b.delta = ddelta;
+    hipLaunchKernelGGL(spr_scan_kernel, dim3((unsigned)nm * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
+    hipLaunchKernelGGL(nni_sum_kernel, dim3((unsigned)nm), dim3(64), 0, 0, b);
+  };
+  return bl_scan(h, "CB_SPR_LL_BYTES", n_moves, off_m, has, recs.data(), SPR_REC, launch, delta, ll_moves, fam_ll, kernel_ms);
 }
 
 constexpr size_t SUP_BYTES = (size_t)256 << 20;   // ll'[move][unit] and C[move][replicate] of one chunk of whole groups, at most (one
@@ -513,12 +529,10 @@ extern "C" int cb_bl_supports(cb_bl_s *h, int n_rep, const uint64_t *seeds, cons
   // every triple and the grouping, on the host, before any device work
   const EmForestHost &H = h->forest.host;
   const int n_fam = H.n_fam(), S = h->forest.S;
-  std::vector<size_t> off_m(n_fam + 1, 0), off_g(n_fam + 1, 0);
-  for (int f = 0; f < n_fam; ++f) {
-    if (n_moves[f] < 0) return fail(CB_EINVAL, "%s: family %d: n_moves = %d", who, f, n_moves[f]);
-    off_m[f + 1] = off_m[f] + n_moves[f];
-  }
-  if (off_m[n_fam] > 0 && !moves) return fail(CB_EINVAL, "%s: NULL argument", who);
+  std::vector<size_t> off_m, off_g(n_fam + 1, 0);
+  std::vector<char> has;
+  int rc = bl_move_lists(who, H, n_moves, moves, off_m, has);
+  if (rc != CB_OK) return rc;
   std::vector<int> group_ptr;                    // per family its groups' first moves and the end, within the family
   std::vector<size_t> off_gp(n_fam + 1, 0);      // ... where they start in group_ptr
   std::vector<std::vector<int>> cuts(n_fam);     // per family the groups at which its chunks start, and the end
@@ -528,8 +542,7 @@ extern "C" int cb_bl_supports(cb_bl_s *h, int n_rep, const uint64_t *seeds, cons
   for (int f = 0; f < n_fam; ++f) {
     const EmFamHost &F = H.fam[f];
     const int *mv = moves + 3 * off_m[f];
-    const int rc_f = bl_check_moves(who, H, f, n_moves[f], mv);
-    if (rc_f != CB_OK) return rc_f;
+    if ((rc = bl_check_moves(who, H, f, n_moves[f], mv)) != CB_OK) return rc;
     std::vector<char> seen(F.n_nodes, 0);
     for (int m = 0; m < n_moves[f]; ++m) {
       const int v = mv[3 * (size_t)m];
@@ -544,7 +557,7 @@ extern "C" int cb_bl_supports(cb_bl_s *h, int n_rep, const uint64_t *seeds, cons
     off_gp[f + 1] = group_ptr.size();
     const size_t n_groups = off_gp[f + 1] - off_gp[f] - 1;
     off_g[f + 1] = off_g[f] + n_groups;
-    if (n_moves[f] == 0) continue;
+    if (!has[f]) continue;
     // chunks of whole groups: the byte bound, and the tiles of the scan's and the product's launches below 2^31
     const int *gp = group_ptr.data() + off_gp[f];
     const size_t n_blocks = ((size_t)F.n_units + 64 / S - 1) / (64 / S);
@@ -570,15 +583,7 @@ extern "C" int cb_bl_supports(cb_bl_s *h, int n_rep, const uint64_t *seeds, cons
   if (off_g[n_fam] > 0 && (!alrt || !sh_count || !rell_count)) return fail(CB_EINVAL, "%s: NULL argument", who);
   if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0.0;
   if (max_moves > 0) {
-    HIP_TRY(hipSetDevice(h->forest.device));
-    // the messages of the families that are scanned, at the current indices: after a round the resident ones are its start's
-    CbKernelTimer passes(kernel_ms != nullptr, h->ev[0], h->ev[1]);
-    int rc = passes.begin(false);
-    if (rc != CB_OK) return rc;
-    for (int f = 0; f < n_fam; ++f)
-      if (n_moves[f] > 0) bl_launch_passes(h, f, true);
-    HIP_TRY(hipGetLastError());
-    if ((rc = passes.end(kernel_ms)) != CB_OK) return rc;
+    if ((rc = bl_refresh(h, has, kernel_ms)) != CB_OK) return rc;
     std::vector<int> inv(max_units);
     CbDevBufs bufs;   // this call's: freed on every return path
     int *dmoves = bufs.up<int>(nullptr, 3 * max_moves, rc), *dgp = bufs.up<int>(nullptr, max_groups + 1, rc);
@@ -589,31 +594,21 @@ extern "C" int cb_bl_supports(cb_bl_s *h, int n_rep, const uint64_t *seeds, cons
     int *dsh = bufs.up<int>(nullptr, max_groups, rc), *drell = bufs.up<int>(nullptr, max_groups, rc);
     if (rc != CB_OK) return rc;
     for (int f = 0; f < n_fam; ++f) {
-      if (n_moves[f] == 0) continue;
+      if (!has[f]) continue;
       const EmFamView w = h->forest.view(f);
-      const EmFamHost &F = w.F;
-      const int U = F.n_units, *gp = group_ptr.data() + off_gp[f];
+      const int U = w.F.n_units, *gp = group_ptr.data() + off_gp[f];
       const size_t n_groups = off_g[f + 1] - off_g[f];
-      for (int k = 0; k < U; ++k) inv[F.perm[k]] = k;
       HIP_TRY(hipMemcpy(dmoves, moves + 3 * off_m[f], 3 * (size_t)n_moves[f] * sizeof(int), hipMemcpyHostToDevice));
       HIP_TRY(hipMemcpy(dgp, gp, (n_groups + 1) * sizeof(int), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(dinv, inv.data(), (size_t)U * sizeof(int), hipMemcpyHostToDevice));
       // the multiplicities of every replicate, once per family: every edge resamples the same sites
-      SupWeightArgs wa{};
-      wa.n_units = U; wa.k0 = (uint32_t)(seeds[f] & 0xFFFFFFFFu); wa.k1 = (uint32_t)(seeds[f] >> 32); wa.inv = dinv; wa.W = dW;
-      {
-        CbKernelTimer draw(kernel_ms != nullptr, h->ev[0], h->ev[1]);
-        double ms = 0.0;
-        if ((rc = draw.begin(false)) != CB_OK) return rc;
+      SupWeightArgs wa;
+      if ((rc = bl_weight_args(w.F, seeds[f], inv, dinv, dW, wa)) != CB_OK) return rc;
+      rc = bl_timed(h, kernel_ms, 2, [&](CbKernelTimer &) -> int {
         hipLaunchKernelGGL(sup_weights_kernel, dim3((unsigned)n_rep), dim3(256), 0, 0, wa);
-        HIP_TRY(hipGetLastError());
-        if ((rc = draw.end(&ms)) != CB_OK) return rc;
-        if (kernel_ms) kernel_ms[2] += ms;
-      }
-      NniArgs a{};
-      a.S = S; a.n_units = U; a.n_cats = F.n_cats; a.root = F.root; a.n_blocks = w.n_blocks;
-      a.parent = w.parent; a.child_ptr = w.child_ptr; a.child_idx = w.child_idx; a.qb = w.qb; a.unit_cat = w.unit_cat; a.P = h->dP;
-      a.pi_root = h->dpi; a.msg = w.msg; a.U = w.U; a.ll = w.ll; a.out = dout;
+        return CB_OK;
+      });
+      if (rc != CB_OK) return rc;
+      NniArgs a = bl_nni_args(h, w, dout);
       for (size_t ci = 0; ci + 1 < cuts[f].size(); ++ci) {
         const int g0 = cuts[f][ci], g1 = cuts[f][ci + 1], m0 = gp[g0], nm = gp[g1] - m0;
         a.moves = dmoves + 3 * (size_t)m0;
@@ -623,17 +618,16 @@ extern "C" int cb_bl_supports(cb_bl_s *h, int n_rep, const uint64_t *seeds, cons
         SupEdgeArgs ea{};
         ea.n_rep = n_rep; ea.move0 = m0; ea.group_ptr = dgp + g0; ea.delta = a.delta; ea.C = dC;
         ea.alrt = dalrt + g0; ea.sh_count = dsh + g0; ea.rell_count = drell + g0;
-        CbKernelTimer scan(kernel_ms != nullptr, h->ev[0], h->ev[2], h->ev[1]);
-        double ms[2] = {0.0, 0.0};
-        if ((rc = scan.begin(false)) != CB_OK) return rc;
-        hipLaunchKernelGGL(nni_scan_kernel, dim3((unsigned)nm * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
-        hipLaunchKernelGGL(nni_sum_kernel, dim3((unsigned)nm), dim3(64), 0, 0, a);
-        if ((rc = scan.lap()) != CB_OK) return rc;
-        hipLaunchKernelGGL(sup_gemm_kernel, dim3((unsigned)(((size_t)nm + 15) / 16 * rep_tiles)), dim3(256), 0, 0, ga, (int)rep_tiles);
-        hipLaunchKernelGGL(sup_edge_kernel, dim3((unsigned)(g1 - g0)), dim3(256), 0, 0, ea);
-        HIP_TRY(hipGetLastError());
-        if ((rc = scan.end(ms)) != CB_OK) return rc;
-        if (kernel_ms) kernel_ms[1] += ms[0], kernel_ms[2] += ms[1];
+        rc = bl_timed(h, kernel_ms, 1, [&](CbKernelTimer &timer) -> int {
+          hipLaunchKernelGGL(nni_scan_kernel, dim3((unsigned)nm * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
+          hipLaunchKernelGGL(nni_sum_kernel, dim3((unsigned)nm), dim3(64), 0, 0, a);
+          const int rc_lap = timer.lap();
+          if (rc_lap != CB_OK) return rc_lap;
+          hipLaunchKernelGGL(sup_gemm_kernel, dim3((unsigned)(((size_t)nm + 15) / 16 * rep_tiles)), dim3(256), 0, 0, ga, (int)rep_tiles);
+          hipLaunchKernelGGL(sup_edge_kernel, dim3((unsigned)(g1 - g0)), dim3(256), 0, 0, ea);
+          return CB_OK;
+        });
+        if (rc != CB_OK) return rc;
         // (the next chunk writes the same buffers: stream order puts it behind this chunk's kernels and this copy)
         if (delta_rep)
           HIP_TRY(hipMemcpy(delta_rep + (off_m[f] + m0) * n_rep, dC, (size_t)nm * n_rep * sizeof(double), hipMemcpyDeviceToHost));
@@ -642,17 +636,8 @@ extern "C" int cb_bl_supports(cb_bl_s *h, int n_rep, const uint64_t *seeds, cons
       HIP_TRY(hipMemcpy(sh_count + off_g[f], dsh, n_groups * sizeof(int), hipMemcpyDeviceToHost));
       HIP_TRY(hipMemcpy(rell_count + off_g[f], drell, n_groups * sizeof(int), hipMemcpyDeviceToHost));
     }
-    // dll of the scanned families now holds l_u at the current indices -- the bits cb_bl_get's inside pass would write
-    std::vector<char> stale(n_fam);
-    for (int f = 0; f < n_fam; ++f) stale[f] = n_moves[f] > 0 && !h->ll_fresh[f];
-    rc = bl_read_ll(h, stale, nullptr);
-    if (rc != CB_OK) return rc;
-    for (int f = 0; f < n_fam; ++f)
-      if (stale[f]) h->ll_fresh[f] = 1;
   }
-  if (fam_ll)
-    for (int f = 0; f < n_fam; ++f) fam_ll[f] = h->ll_fresh[f] ? h->fam_ll[f] : std::nan("");
-  return CB_OK;
+  return bl_finish(h, has, fam_ll);
 }
 
 constexpr size_t UFB_BYTES = (size_t)256 << 20;   // ll'[move][unit] of one chunk of moves, at most (one tile of 16 moves always
@@ -668,25 +653,22 @@ extern "C" int cb_bl_bootstrap_best(cb_bl_s *h, int n_rep, const uint64_t *seeds
   // every triple and every incoming score, on the host, before any device work
   const EmForestHost &H = h->forest.host;
   const int n_fam = H.n_fam(), S = h->forest.S;
-  std::vector<size_t> off_m(n_fam + 1, 0);
-  for (int f = 0; f < n_fam; ++f) {
-    if (n_moves[f] < 0) return fail(CB_EINVAL, "%s: family %d: n_moves = %d", who, f, n_moves[f]);
-    off_m[f + 1] = off_m[f] + n_moves[f];
-  }
-  if (off_m[n_fam] > 0 && !moves) return fail(CB_EINVAL, "%s: NULL argument", who);
+  std::vector<size_t> off_m;
+  std::vector<char> has;
+  int rc = bl_move_lists(who, H, n_moves, moves, off_m, has);
+  if (rc != CB_OK) return rc;
   const size_t bound = cb_hook_bytes("CB_UFB_BYTES", UFB_BYTES);
   const int rep_tiles = (n_rep + UFB_RT - 1) / UFB_RT;
   std::vector<int> chunk(n_fam, 0);
   size_t max_moves = 0, max_out = 0, max_units = 0, max_slices = 1;
   for (int f = 0; f < n_fam; ++f) {
     const EmFamHost &F = H.fam[f];
-    const int rc_f = bl_check_moves(who, H, f, n_moves[f], moves + 3 * off_m[f]);
-    if (rc_f != CB_OK) return rc_f;
+    if ((rc = bl_check_moves(who, H, f, n_moves[f], moves + 3 * off_m[f])) != CB_OK) return rc;
     for (int r = 0; r < n_rep; ++r)
       if (std::isnan(best_score[(size_t)f * n_rep + r]))
         return fail(CB_EINVAL, "%s: family %d replicate %d: the incoming best score is NaN", who, f, r);
     max_units = std::max(max_units, (size_t)F.n_units);
-    if (n_moves[f] == 0) continue;
+    if (!has[f]) continue;
     // chunks of whole move tiles: the byte bound, and the scan's launch below 2^31 blocks
     const size_t n_blocks = ((size_t)F.n_units + 64 / S - 1) / (64 / S);
     const size_t fit = std::max<size_t>(bound / ((size_t)F.n_units * sizeof(double)) / 16 * 16, 16);
@@ -698,14 +680,8 @@ extern "C" int cb_bl_bootstrap_best(cb_bl_s *h, int n_rep, const uint64_t *seeds
     max_slices = std::max(max_slices, std::min<size_t>(((size_t)chunk[f] + 15) / 16, std::max(1, UFB_WORKGROUPS / rep_tiles)));
   }
   if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0.0;
-  HIP_TRY(hipSetDevice(h->forest.device));
-  // the messages and l_u of every family at the current indices: after a round the resident ones are its start's
-  CbKernelTimer passes(kernel_ms != nullptr, h->ev[0], h->ev[1]);
-  int rc = passes.begin(false);
-  if (rc != CB_OK) return rc;
-  for (int f = 0; f < n_fam; ++f) bl_launch_passes(h, f, true);
-  HIP_TRY(hipGetLastError());
-  if ((rc = passes.end(kernel_ms)) != CB_OK) return rc;
+  const std::vector<char> all(n_fam, 1);   // a family with no move still scores its tree
+  if ((rc = bl_refresh(h, all, kernel_ms)) != CB_OK) return rc;
   std::vector<int> inv(max_units);
   CbDevBufs bufs;   // this call's: freed on every return path
   int *dmoves = bufs.up<int>(nullptr, 3 * max_moves, rc), *dinv = bufs.up<int>(nullptr, max_units, rc);
@@ -716,16 +692,12 @@ extern "C" int cb_bl_bootstrap_best(cb_bl_s *h, int n_rep, const uint64_t *seeds
   if (rc != CB_OK) return rc;
   for (int f = 0; f < n_fam; ++f) {
     const EmFamView w = h->forest.view(f);
-    const EmFamHost &F = w.F;
-    const int U = F.n_units;
-    for (int k = 0; k < U; ++k) inv[F.perm[k]] = k;
-    if (n_moves[f] > 0)
-      HIP_TRY(hipMemcpy(dmoves, moves + 3 * off_m[f], 3 * (size_t)n_moves[f] * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dinv, inv.data(), (size_t)U * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dbest, best_score + (size_t)f * n_rep, (size_t)n_rep * sizeof(double), hipMemcpyHostToDevice));
+    const int U = w.F.n_units;
+    if (has[f]) HIP_TRY(hipMemcpy(dmoves, moves + 3 * off_m[f], 3 * (size_t)n_moves[f] * sizeof(int), hipMemcpyHostToDevice));
     // the multiplicities of every replicate, once per family, and the tree's own resampled log-likelihood
-    SupWeightArgs wa{};
-    wa.n_units = U; wa.k0 = (uint32_t)(seeds[f] & 0xFFFFFFFFu); wa.k1 = (uint32_t)(seeds[f] >> 32); wa.inv = dinv; wa.W = dW;
+    SupWeightArgs wa;
+    if ((rc = bl_weight_args(w.F, seeds[f], inv, dinv, dW, wa)) != CB_OK) return rc;
+    HIP_TRY(hipMemcpy(dbest, best_score + (size_t)f * n_rep, (size_t)n_rep * sizeof(double), hipMemcpyHostToDevice));
     UfbGemmArgs ga{};
     ga.n_rep = n_rep; ga.n_units = U; ga.out = dout; ga.ll = w.ll; ga.W = dW; ga.base = dbase; ga.part_score = dpart;
     ga.part_code = dpcode;
@@ -733,21 +705,14 @@ extern "C" int cb_bl_bootstrap_best(cb_bl_s *h, int n_rep, const uint64_t *seeds
     ma.n_rep = n_rep; ma.first = 1; ma.base = dbase; ma.part_score = dpart; ma.part_code = dpcode; ma.best_score = dbest;
     ma.best_code = dcode;
     const unsigned merge_grid = (unsigned)((n_rep + 255) / 256);
-    {
-      CbKernelTimer draw(kernel_ms != nullptr, h->ev[0], h->ev[1]);
-      double ms = 0.0;
-      if ((rc = draw.begin(false)) != CB_OK) return rc;
+    rc = bl_timed(h, kernel_ms, 2, [&](CbKernelTimer &) -> int {
       hipLaunchKernelGGL(sup_weights_kernel, dim3((unsigned)n_rep), dim3(256), 0, 0, wa);
       hipLaunchKernelGGL(ufb_gemm_kernel<true>, dim3((unsigned)rep_tiles), dim3(256), 0, 0, ga, rep_tiles);
-      if (n_moves[f] == 0) hipLaunchKernelGGL(ufb_merge_kernel, dim3(merge_grid), dim3(256), 0, 0, ma);   // the tree against the incoming best
-      HIP_TRY(hipGetLastError());
-      if ((rc = draw.end(&ms)) != CB_OK) return rc;
-      if (kernel_ms) kernel_ms[2] += ms;
-    }
-    NniArgs a{};
-    a.S = S; a.n_units = U; a.n_cats = F.n_cats; a.root = F.root; a.n_blocks = w.n_blocks;
-    a.parent = w.parent; a.child_ptr = w.child_ptr; a.child_idx = w.child_idx; a.qb = w.qb; a.unit_cat = w.unit_cat; a.P = h->dP;
-    a.pi_root = h->dpi; a.msg = w.msg; a.U = w.U; a.ll = w.ll; a.out = dout;
+      if (!has[f]) hipLaunchKernelGGL(ufb_merge_kernel, dim3(merge_grid), dim3(256), 0, 0, ma);   // the tree against the incoming best
+      return CB_OK;
+    });
+    if (rc != CB_OK) return rc;
+    NniArgs a = bl_nni_args(h, w, dout);
     for (int m0 = 0; m0 < n_moves[f]; m0 += chunk[f]) {
       const int nm = std::min(chunk[f], n_moves[f] - m0);
       a.moves = dmoves + 3 * (size_t)m0;
@@ -755,31 +720,23 @@ extern "C" int cb_bl_bootstrap_best(cb_bl_s *h, int n_rep, const uint64_t *seeds
       ga.n_moves = nm; ga.move0 = m0; ga.delta = a.delta; ga.n_tiles = (nm + 15) / 16;
       ga.n_slices = std::min(ga.n_tiles, std::max(1, UFB_WORKGROUPS / rep_tiles));
       ma.n_slices = ga.n_slices; ma.first = m0 == 0;
-      CbKernelTimer scan(kernel_ms != nullptr, h->ev[0], h->ev[2], h->ev[1]);
-      double ms[2] = {0.0, 0.0};
-      if ((rc = scan.begin(false)) != CB_OK) return rc;
-      hipLaunchKernelGGL(nni_scan_kernel, dim3((unsigned)nm * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
-      hipLaunchKernelGGL(nni_sum_kernel, dim3((unsigned)nm), dim3(64), 0, 0, a);
-      if ((rc = scan.lap()) != CB_OK) return rc;
-      hipLaunchKernelGGL(ufb_gemm_kernel<false>, dim3((unsigned)(ga.n_slices * rep_tiles)), dim3(256), 0, 0, ga, rep_tiles);
-      hipLaunchKernelGGL(ufb_merge_kernel, dim3(merge_grid), dim3(256), 0, 0, ma);
-      HIP_TRY(hipGetLastError());
-      if ((rc = scan.end(ms)) != CB_OK) return rc;
-      if (kernel_ms) kernel_ms[1] += ms[0], kernel_ms[2] += ms[1];
+      rc = bl_timed(h, kernel_ms, 1, [&](CbKernelTimer &timer) -> int {
+        hipLaunchKernelGGL(nni_scan_kernel, dim3((unsigned)nm * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
+        hipLaunchKernelGGL(nni_sum_kernel, dim3((unsigned)nm), dim3(64), 0, 0, a);
+        const int rc_lap = timer.lap();
+        if (rc_lap != CB_OK) return rc_lap;
+        hipLaunchKernelGGL(ufb_gemm_kernel<false>, dim3((unsigned)(ga.n_slices * rep_tiles)), dim3(256), 0, 0, ga, rep_tiles);
+        hipLaunchKernelGGL(ufb_merge_kernel, dim3(merge_grid), dim3(256), 0, 0, ma);
+        return CB_OK;
+      });
+      if (rc != CB_OK) return rc;
       // (the next chunk writes the same buffers: stream order puts it behind this chunk's kernels)
     }
     HIP_TRY(hipMemcpy(best_score + (size_t)f * n_rep, dbest, (size_t)n_rep * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(best_code + (size_t)f * n_rep, dcode, (size_t)n_rep * sizeof(int), hipMemcpyDeviceToHost));
     if (base) HIP_TRY(hipMemcpy(base + (size_t)f * n_rep, dbase, (size_t)n_rep * sizeof(double), hipMemcpyDeviceToHost));
   }
-  // dll now holds l_u at the current indices -- the bits cb_bl_get's inside pass would write
-  std::vector<char> stale(n_fam);
-  for (int f = 0; f < n_fam; ++f) stale[f] = !h->ll_fresh[f];
-  rc = bl_read_ll(h, stale, nullptr);
-  if (rc != CB_OK) return rc;
-  std::fill(h->ll_fresh.begin(), h->ll_fresh.end(), 1);
-  if (fam_ll) std::copy(h->fam_ll.begin(), h->fam_ll.end(), fam_ll);
-  return CB_OK;
+  return bl_finish(h, all, fam_ll);
 }
 
 constexpr size_t ANC_POST_BYTES =(size_t)256 << 20;   // post[node][unit][S] of one chunk of nodes, at most (one node always goes);
@@ -805,15 +762,10 @@ extern "C" int cb_bl_ancestral(cb_bl_s *h, int8_t *state, double *conf, double *
       return fail(CB_EINVAL, "%s: family %d: %zu site tiles (at most 2^31 - 1 per launch)", who, f, n_blocks);
     max_out = std::max(max_out, (size_t)chunk[f] * F.n_units);
   }
-  HIP_TRY(hipSetDevice(h->forest.device));
   if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.0;
-  // the messages at the current indices: after a round the resident ones are its start's
-  CbKernelTimer passes(kernel_ms != nullptr, h->ev[0], h->ev[1]);
-  int rc = passes.begin(false);
+  const std::vector<char> all(n_fam, 1);
+  int rc = bl_refresh(h, all, kernel_ms);
   if (rc != CB_OK) return rc;
-  for (int f = 0; f < n_fam; ++f) bl_launch_passes(h, f, true);
-  HIP_TRY(hipGetLastError());
-  if ((rc = passes.end(kernel_ms)) != CB_OK) return rc;
   std::vector<int8_t> host_state(max_out);
   std::vector<double> host_conf(conf ? max_out : 0), host_post(post ? max_out * S : 0);
   CbDevBufs bufs;   // this call's: freed on every return path
@@ -831,13 +783,11 @@ extern "C" int cb_bl_ancestral(cb_bl_s *h, int8_t *state, double *conf, double *
     for (int v0 = 0; v0 < F.n_nodes; v0 += chunk[f]) {
       const int nv = std::min(chunk[f], F.n_nodes - v0);
       a.node0 = v0;
-      CbKernelTimer recon(kernel_ms != nullptr, h->ev[0], h->ev[1]);
-      double ms = 0.0;
-      if ((rc = recon.begin(false)) != CB_OK) return rc;
-      hipLaunchKernelGGL(anc_post_kernel, dim3((unsigned)nv * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
-      HIP_TRY(hipGetLastError());
-      if ((rc = recon.end(&ms)) != CB_OK) return rc;
-      if (kernel_ms) kernel_ms[1] += ms;
+      rc = bl_timed(h, kernel_ms, 1, [&](CbKernelTimer &) -> int {
+        hipLaunchKernelGGL(anc_post_kernel, dim3((unsigned)nv * (unsigned)a.n_blocks), dim3(64), 0, 0, a);
+        return CB_OK;
+      });
+      if (rc != CB_OK) return rc;
       // device (category) order -> the caller's unit order (the next chunk writes the same buffers: these copies wait for this one)
       const size_t cnt = (size_t)nv * U, base = H.off_c[f] + (size_t)v0 * U;
       HIP_TRY(hipMemcpy(host_state.data(), dstate, cnt * sizeof(int8_t), hipMemcpyDeviceToHost));
@@ -854,12 +804,5 @@ extern "C" int cb_bl_ancestral(cb_bl_s *h, int8_t *state, double *conf, double *
         }
     }
   }
-  // dll now holds l_u at the current indices -- the bits cb_bl_get's inside pass would write
-  std::vector<char> stale(n_fam);
-  for (int f = 0; f < n_fam; ++f) stale[f] = !h->ll_fresh[f];
-  rc = bl_read_ll(h, stale, nullptr);
-  if (rc != CB_OK) return rc;
-  std::fill(h->ll_fresh.begin(), h->ll_fresh.end(), 1);
-  if (fam_ll) std::copy(h->fam_ll.begin(), h->fam_ll.end(), fam_ll);
-  return CB_OK;
+  return bl_finish(h, all, fam_ll);
 }

@@ -17,7 +17,7 @@ Out of scope: changing a handle's topology in place, a continuous (off-grid) opt
 import ctypes
 import os
 import time
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -107,6 +107,45 @@ class BranchLengthFitter(_lib.ResidentHandle):
         _, ll, fam = self._get(True)
         return np.split(ll, np.cumsum(self.n_units)[:-1]), fam
 
+    def _call(self, name: str, *args) -> None:
+        """the library call `name` on the handle; a refused argument (CB_EINVAL) is a `CherryBankError` with the library's
+        message, which names family, move and value"""
+        rc = getattr(_lib.load(), name)(self._handle(), *args)
+        if rc == _lib.CB_EINVAL:
+            raise _lib.CherryBankError(f"{name} failed ({rc}): {_lib.load().cb_last_error().decode('utf-8', 'replace')}")
+        _lib.check(rc, name)
+
+    def _move_lists(self, who: str, moves: Optional[Sequence], width: int, default):
+        """one list per family as int32 [n, width] (`default()` when None) -> (moves, n_moves [n_fam], all of them flat)"""
+        moves = default() if moves is None else [np.ascontiguousarray(m, dtype=np.int32).reshape(-1, width) for m in moves]
+        if len(moves) != self.n_nodes.size:
+            raise ValueError(f"{who}: {len(moves)} move lists for {self.n_nodes.size} families")
+        n_moves = np.array([len(m) for m in moves], dtype=np.int32)
+        return moves, n_moves, np.ascontiguousarray(np.concatenate(moves).reshape(-1), dtype=np.int32)
+
+    def _seed_array(self, who: str, seeds: Optional[Sequence[int]]) -> np.ndarray:
+        """one 64-bit seed per family (default 0) as uint64"""
+        seeds = [0] * self.n_nodes.size if seeds is None else [int(s) for s in seeds]
+        if len(seeds) != self.n_nodes.size:
+            raise ValueError(f"{who}: {len(seeds)} seeds for {self.n_nodes.size} families")
+        return np.array([s & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=np.uint64)
+
+    def _scan(self, who: str, moves: Optional[Sequence], width: int, default, per_site: bool):
+        """`nni_scan` and `spr_scan`: the library's `cb_bl_<who>` on lists of `width` ints per move -> (its kernel_ms, the
+        method's result)"""
+        moves, n_moves, flat = self._move_lists(who, moves, width, default)
+        delta = np.empty(int(n_moves.sum()))
+        sizes = n_moves.astype(np.int64) * self.n_units
+        ll = np.empty(int(sizes.sum())) if per_site else None
+        ms = (ctypes.c_double * 2)(0.0, 0.0)
+        self._call("cb_bl_" + who, n_moves.ctypes.data, flat.ctypes.data, delta.ctypes.data,
+                   ll.ctypes.data if per_site else None, None, ctypes.addressof(ms))
+        deltas = np.split(delta, np.cumsum(n_moves)[:-1])
+        if not per_site:
+            return (ms[0], ms[1]), (moves, deltas)
+        lls = [x.reshape(int(k), int(u)) for x, k, u in zip(np.split(ll, np.cumsum(sizes)[:-1]), n_moves, self.n_units)]
+        return (ms[0], ms[1]), (moves, deltas, lls)
+
     def nni_moves(self) -> List[np.ndarray]:
         """per family the int32 [n, 3] array of ALL nearest-neighbour interchanges (v, c, s) of its tree, node indices in
         `tree.nodes()` order: v (internal, not the root) ascending, then c over the children of v, then s over the other children
@@ -120,26 +159,8 @@ class BranchLengthFitter(_lib.ResidentHandle):
         none is skipped), delta [n] = the log-likelihood of the rearranged tree minus the present one, and ll_moves [n, n_sites]
         the rearranged tree's log-likelihood per site.  Changes nothing `round()`, `indices()` or `log_likelihoods()` return.
         Sets `last_nni_kernel_ms` = (passes, scan)."""
-        moves = self.nni_moves() if moves is None else [np.ascontiguousarray(m, dtype=np.int32).reshape(-1, 3) for m in moves]
-        if len(moves) != self.n_nodes.size:
-            raise ValueError(f"nni_scan: {len(moves)} move lists for {self.n_nodes.size} families")
-        n_moves = np.array([len(m) for m in moves], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate(moves).reshape(-1), dtype=np.int32)
-        delta = np.empty(int(n_moves.sum()))
-        sizes = n_moves.astype(np.int64) * self.n_units
-        ll = np.empty(int(sizes.sum())) if per_site else None
-        ms = (ctypes.c_double * 2)(0.0, 0.0)
-        rc = _lib.load().cb_bl_nni_scan(self._handle(), n_moves.ctypes.data, flat.ctypes.data, delta.ctypes.data,
-                                        ll.ctypes.data if per_site else None, None, ctypes.addressof(ms))
-        if rc == _lib.CB_EINVAL:   # a refused move list: the library's message names family, move and value
-            raise _lib.CherryBankError(f"cb_bl_nni_scan failed ({rc}): {_lib.load().cb_last_error().decode('utf-8', 'replace')}")
-        _lib.check(rc, "cb_bl_nni_scan")
-        self.last_nni_kernel_ms = (ms[0], ms[1])
-        deltas = np.split(delta, np.cumsum(n_moves)[:-1])
-        if not per_site:
-            return moves, deltas
-        lls = [x.reshape(int(k), int(u)) for x, k, u in zip(np.split(ll, np.cumsum(sizes)[:-1]), n_moves, self.n_units)]
-        return moves, deltas, lls
+        self.last_nni_kernel_ms, out = self._scan("nni_scan", moves, 3, self.nni_moves, per_site)
+        return out
 
     def spr_moves(self, radius: int = 3) -> List[np.ndarray]:
         """per family the int32 [n, 5] array of ALL subtree prune-and-regraft moves (x, y, tau_s, tau_p, tau_y) of its tree within
@@ -154,26 +175,8 @@ class BranchLengthFitter(_lib.ResidentHandle):
         (`spr_moves(radius)` when None; a family with none is skipped), delta [n] = the log-likelihood of the rearranged tree
         at the move's three indices minus the present one, and ll_moves [n, n_sites] the rearranged tree's log-likelihood per
         site.  Changes nothing any other method returns.  Sets `last_spr_kernel_ms` = (passes, scan)."""
-        moves = self.spr_moves(radius) if moves is None else [np.ascontiguousarray(m, dtype=np.int32).reshape(-1, 5) for m in moves]
-        if len(moves) != self.n_nodes.size:
-            raise ValueError(f"spr_scan: {len(moves)} move lists for {self.n_nodes.size} families")
-        n_moves = np.array([len(m) for m in moves], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate(moves).reshape(-1), dtype=np.int32)
-        delta = np.empty(int(n_moves.sum()))
-        sizes = n_moves.astype(np.int64) * self.n_units
-        ll = np.empty(int(sizes.sum())) if per_site else None
-        ms = (ctypes.c_double * 2)(0.0, 0.0)
-        rc = _lib.load().cb_bl_spr_scan(self._handle(), n_moves.ctypes.data, flat.ctypes.data, delta.ctypes.data,
-                                        ll.ctypes.data if per_site else None, None, ctypes.addressof(ms))
-        if rc == _lib.CB_EINVAL:   # a refused move list: the library's message names family, move and value
-            raise _lib.CherryBankError(f"cb_bl_spr_scan failed ({rc}): {_lib.load().cb_last_error().decode('utf-8', 'replace')}")
-        _lib.check(rc, "cb_bl_spr_scan")
-        self.last_spr_kernel_ms = (ms[0], ms[1])
-        deltas = np.split(delta, np.cumsum(n_moves)[:-1])
-        if not per_site:
-            return moves, deltas
-        lls = [x.reshape(int(k), int(u)) for x, k, u in zip(np.split(ll, np.cumsum(sizes)[:-1]), n_moves, self.n_units)]
-        return moves, deltas, lls
+        self.last_spr_kernel_ms, out = self._scan("spr_scan", moves, 5, lambda: self.spr_moves(radius), per_site)
+        return out
 
     def branch_supports(self, num_replicates: int = 1000, seeds: Optional[Sequence[int]] = None, per_replicate: bool = False,
                         moves: Optional[Sequence] = None):
@@ -188,17 +191,9 @@ class BranchLengthFitter(_lib.ResidentHandle):
         `nni_moves()`, equal v consecutive (a subset of the edges, or of an edge's neighbours).  Changes nothing
         `round()`, `indices()`, `log_likelihoods()`, `nni_scan()` or `ancestral_states()` return.  Sets
         `last_support_kernel_ms` = (passes, scan, resampling)."""
-        n_fam = self.n_nodes.size
         num_replicates = int(num_replicates)
-        seeds = [0] * n_fam if seeds is None else [int(s) for s in seeds]
-        if len(seeds) != n_fam:
-            raise ValueError(f"branch_supports: {len(seeds)} seeds for {n_fam} families")
-        seed_arr = np.array([s & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=np.uint64)
-        moves = self.nni_moves() if moves is None else [np.ascontiguousarray(m, dtype=np.int32).reshape(-1, 3) for m in moves]
-        if len(moves) != n_fam:
-            raise ValueError(f"branch_supports: {len(moves)} move lists for {n_fam} families")
-        n_moves = np.array([len(m) for m in moves], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate(moves).reshape(-1), dtype=np.int32)
+        seed_arr = self._seed_array("branch_supports", seeds)
+        moves, n_moves, flat = self._move_lists("branch_supports", moves, 3, self.nni_moves)
         # the groups: runs of equal v (the library refuses a v that comes back)
         nodes = [m[np.r_[True, m[1:, 0] != m[:-1, 0]], 0].astype(np.int32) if len(m) else np.zeros(0, dtype=np.int32) for m in moves]
         n_groups = np.array([len(v) for v in nodes], dtype=np.int64)
@@ -207,12 +202,8 @@ class BranchLengthFitter(_lib.ResidentHandle):
         sh, rell = np.empty(total, dtype=np.int32), np.empty(total, dtype=np.int32)
         rep = np.empty(int(n_moves.sum()) * max(num_replicates, 0)) if per_replicate else None
         ms = (ctypes.c_double * 3)(0.0, 0.0, 0.0)
-        rc = _lib.load().cb_bl_supports(self._handle(), num_replicates, seed_arr.ctypes.data, n_moves.ctypes.data, flat.ctypes.data,
-                                        alrt.ctypes.data, sh.ctypes.data, rell.ctypes.data, rep.ctypes.data if per_replicate else None,
-                                        None, ctypes.addressof(ms))
-        if rc == _lib.CB_EINVAL:   # a refused call: the library's message names the value
-            raise _lib.CherryBankError(f"cb_bl_supports failed ({rc}): {_lib.load().cb_last_error().decode('utf-8', 'replace')}")
-        _lib.check(rc, "cb_bl_supports")
+        self._call("cb_bl_supports", num_replicates, seed_arr.ctypes.data, n_moves.ctypes.data, flat.ctypes.data, alrt.ctypes.data,
+                   sh.ctypes.data, rell.ctypes.data, rep.ctypes.data if per_replicate else None, None, ctypes.addressof(ms))
         self.last_support_kernel_ms = (ms[0], ms[1], ms[2])
         cuts = np.cumsum(n_groups)[:-1]
         share = [[np.where(x >= 0, x / num_replicates, np.nan) for x in np.split(c, cuts)] for c in (sh, rell)]
@@ -238,13 +229,8 @@ class BranchLengthFitter(_lib.ResidentHandle):
         n_fam = self.n_nodes.size
         num_replicates = int(num_replicates)
         R = max(num_replicates, 0)
-        seeds = [0] * n_fam if seeds is None else [int(s) for s in seeds]
-        if len(seeds) != n_fam:
-            raise ValueError(f"bootstrap_best: {len(seeds)} seeds for {n_fam} families")
-        seed_arr = np.array([s & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=np.uint64)
-        moves = self.nni_moves() if moves is None else [np.ascontiguousarray(m, dtype=np.int32).reshape(-1, 3) for m in moves]
-        if len(moves) != n_fam:
-            raise ValueError(f"bootstrap_best: {len(moves)} move lists for {n_fam} families")
+        seed_arr = self._seed_array("bootstrap_best", seeds)
+        moves, n_moves, flat = self._move_lists("bootstrap_best", moves, 3, self.nni_moves)
         if best is None:
             score = np.full((n_fam, R), -np.inf)
         else:
@@ -254,18 +240,11 @@ class BranchLengthFitter(_lib.ResidentHandle):
                                          np.zeros((n_fam, 0)))
             if score.shape != (n_fam, R):
                 raise ValueError(f"bootstrap_best: the incoming best has shape {score.shape}, not {(n_fam, R)}")
-        n_moves = np.array([len(m) for m in moves], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate(moves).reshape(-1), dtype=np.int32)
         code = np.empty((n_fam, R), dtype=np.int32)
         own = np.empty((n_fam, R)) if base else None
         ms = (ctypes.c_double * 3)(0.0, 0.0, 0.0)
-        rc = _lib.load().cb_bl_bootstrap_best(self._handle(), num_replicates, seed_arr.ctypes.data, n_moves.ctypes.data,
-                                              flat.ctypes.data, score.ctypes.data, code.ctypes.data,
-                                              own.ctypes.data if base else None, None, ctypes.addressof(ms))
-        if rc == _lib.CB_EINVAL:   # a refused call: the library's message names the value
-            raise _lib.CherryBankError(f"cb_bl_bootstrap_best failed ({rc}): "
-                                       f"{_lib.load().cb_last_error().decode('utf-8', 'replace')}")
-        _lib.check(rc, "cb_bl_bootstrap_best")
+        self._call("cb_bl_bootstrap_best", num_replicates, seed_arr.ctypes.data, n_moves.ctypes.data, flat.ctypes.data,
+                   score.ctypes.data, code.ctypes.data, own.ctypes.data if base else None, None, ctypes.addressof(ms))
         self.last_ufboot_kernel_ms = (ms[0], ms[1], ms[2])
         return [(score[k], code[k], own[k]) if base else (score[k], code[k]) for k in range(n_fam)]
 
@@ -309,6 +288,91 @@ def _batches(bank_bytes: Sequence[int], bound: int) -> List[List[int]]:
     return out
 
 
+class _StageInputs(NamedTuple):
+    """what `ml_branch_lengths` and the searches (`_search.py`) read before their first handle"""
+    families: List[str]
+    output_tree_dir: str
+    output_likelihood_dir: str
+    start: float           # time.time() at the stage's start
+    alphabet: List[str]
+    Q: np.ndarray
+    pi_root: np.ndarray
+    grid: np.ndarray
+    device: int
+    trees: List[Tree]
+    msas: list
+    rates: List[np.ndarray]
+    codes: List[np.ndarray]     # rows in tree.nodes() order, which no move changes
+    bank_bytes: List[int]
+
+    def fitter(self, fams: Sequence[int], trees: Sequence[Tree]) -> BranchLengthFitter:
+        """a handle on `trees`, the trees of the families `fams`"""
+        return BranchLengthFitter(trees, [self.codes[f] for f in fams], [self.rates[f] for f in fams], self.grid, self.Q,
+                                  self.pi_root, device=self.device)
+
+
+def _read_stage_inputs(stage: str, runs: str, tree_dir: str, msa_dir: str, site_rates_dir: str, families: List[str],
+                       rate_matrix_path: str, grid_args: Sequence, output_tree_dir: Optional[str],
+                       output_likelihood_dir: Optional[str]) -> _StageInputs:
+    """the checks of a stage on tree / MSA / site-rate directories (`runs`: what it does, for the no-device message), its output
+    directories, the model, the grid `quantization_points_ble(*grid_args)` and the families' trees, MSAs, site rates and codes"""
+    from ..counting._host import read_msa, read_site_rates
+    from ..counting._stage import _device_index
+    from ..evaluation._likelihood import _family_units, _stationary_distribution
+    from ..io import read_rate_matrix
+    if output_tree_dir is None or output_likelihood_dir is None:
+        raise ValueError("output_tree_dir and output_likelihood_dir are required")
+    if _lib.load().cb_device_count() <= 0:
+        raise _lib.CherryBankError(f"{stage}: no HIP device visible; the {runs} runs on the MI355X only (no CPU fallback)")
+    st_all = time.time()
+    for d in (output_tree_dir, output_likelihood_dir):
+        os.makedirs(d, exist_ok=True)
+    rm = read_rate_matrix(rate_matrix_path)
+    alphabet = [str(c) for c in rm.columns]
+    Q = np.ascontiguousarray(rm.to_numpy(), dtype=np.float64)
+    pi_root = _stationary_distribution(Q)
+    grid = np.array(quantization_points_ble(*grid_args))
+    device = _device_index()
+    trees, msas, rates, codes = [], [], [], []
+    for family in families:
+        tree = read_tree(os.path.join(tree_dir, family + ".txt"))
+        msa = read_msa(os.path.join(msa_dir, family + ".txt"))
+        r = np.asarray(read_site_rates(os.path.join(site_rates_dir, family + ".txt")), dtype=np.float64)
+        trees.append(tree), msas.append(msa), rates.append(r)
+        codes.append(_family_units(tree, msa, None, len(r), alphabet, False)[2])
+    bank_bytes = [2 * grid.size * np.unique(r).size * Q.size * 8 for r in rates]
+    return _StageInputs(families, output_tree_dir, output_likelihood_dir, st_all, alphabet, Q, pi_root, grid, device, trees, msas,
+                        rates, codes, bank_bytes)
+
+
+def _tree_at(tree: Tree, lengths: Dict[str, float]) -> Tree:
+    """`tree` with the lengths of a fitter's `lengths()`: the same nodes and edges in the same order"""
+    t = Tree()
+    t.add_nodes(tree.nodes())
+    t.add_edges([(u, v, lengths[v]) for u, v, _ in tree.edges()])
+    return t
+
+
+def _write_stage_outputs(inp: _StageInputs, trees: Sequence[Tree], logs: Sequence[List[str]], log_ext: str,
+                         profs: Sequence[Dict[str, float]]) -> None:
+    """the likelihoods of the final trees and, per family, the tree, its log `<family><log_ext>`, its likelihoods and
+    `<family>.profiling` (`profs` and the shares of the likelihood and the total time)"""
+    from ..evaluation._likelihood import dp_likelihood_computation_batch, write_log_likelihood
+    F = len(inp.families)
+    st = time.time()
+    lls = dp_likelihood_computation_batch(trees, inp.msas, [None] * F, [[float(x) for x in r] for r in inp.rates], inp.alphabet,
+                                          inp.pi_root, inp.Q, device=inp.device)
+    t_ll = (time.time() - st) / max(F, 1)
+    t_total = (time.time() - inp.start) / max(F, 1)
+    for f, family in enumerate(inp.families):
+        write_tree(trees[f], os.path.join(inp.output_tree_dir, family + ".txt"))
+        with open(os.path.join(inp.output_tree_dir, family + log_ext), "w") as fh:
+            fh.write("".join(logs[f]))
+        write_log_likelihood(lls[f], os.path.join(inp.output_likelihood_dir, family + ".txt"))
+        with open(os.path.join(inp.output_tree_dir, family + ".profiling"), "w") as fh:
+            fh.write("".join(f"{k}: {v}\n" for k, v in profs[f].items()) + f"likelihood_time: {t_ll}\ntotal_time: {t_total}")
+
+
 @cached_computation(output_dirs=["output_tree_dir", "output_likelihood_dir"], exclude_args=["max_bank_bytes"])
 def ml_branch_lengths(tree_dir: str, msa_dir: str, site_rates_dir: str, families: List[str], rate_matrix_path: str,
                       num_rounds: int = 10, quantization_grid_center: float = 0.03, quantization_grid_step: float = 1.1,
@@ -322,39 +386,15 @@ def ml_branch_lengths(tree_dir: str, msa_dir: str, site_rates_dir: str, families
     `nj_trees` writes it (`dp_likelihood_computation_batch` on the written trees, root distribution = the matrix's stationary
     distribution).  All families go in one handle unless their banks would exceed `max_bank_bytes`; then they go in batches in
     family order -- families are independent, so the results do not depend on the batching."""
-    from ..counting._host import read_msa, read_site_rates
-    from ..counting._stage import _device_index
-    from ..evaluation._likelihood import (_family_units, _stationary_distribution, dp_likelihood_computation_batch,
-                                          write_log_likelihood)
-    from ..io import read_rate_matrix
-    if output_tree_dir is None or output_likelihood_dir is None:
-        raise ValueError("output_tree_dir and output_likelihood_dir are required")
-    if _lib.load().cb_device_count() <= 0:
-        raise _lib.CherryBankError("ml_branch_lengths: no HIP device visible; the fit runs on the MI355X only (no CPU fallback)")
-    st_all = time.time()
-    for d in (output_tree_dir, output_likelihood_dir):
-        os.makedirs(d, exist_ok=True)
-    rm = read_rate_matrix(rate_matrix_path)
-    alphabet = [str(c) for c in rm.columns]
-    Q = np.ascontiguousarray(rm.to_numpy(), dtype=np.float64)
-    pi_root = _stationary_distribution(Q)
-    grid = np.array(quantization_points_ble(quantization_grid_center, quantization_grid_step, quantization_grid_num_steps))
-    device = _device_index()
-    trees, msas, rates, codes = [], [], [], []
-    for family in families:
-        tree = read_tree(os.path.join(tree_dir, family + ".txt"))
-        msa = read_msa(os.path.join(msa_dir, family + ".txt"))
-        r = np.asarray(read_site_rates(os.path.join(site_rates_dir, family + ".txt")), dtype=np.float64)
-        trees.append(tree), msas.append(msa), rates.append(r)
-        codes.append(_family_units(tree, msa, None, len(r), alphabet, False)[2])
-    bank_bytes = [2 * grid.size * np.unique(r).size * Q.size * 8 for r in rates]
+    inp = _read_stage_inputs("ml_branch_lengths", "fit", tree_dir, msa_dir, site_rates_dir, families, rate_matrix_path,
+                             (quantization_grid_center, quantization_grid_step, quantization_grid_num_steps), output_tree_dir,
+                             output_likelihood_dir)
     out_trees: List[Optional[Tree]] = [None] * len(families)
     logs: List[List[str]] = [[] for _ in families]
     profs: List[Dict[str, float]] = [{} for _ in families]
-    for batch in _batches(bank_bytes, int(max_bank_bytes)):
+    for batch in _batches(inp.bank_bytes, int(max_bank_bytes)):
         st = time.time()
-        with BranchLengthFitter([trees[f] for f in batch], [codes[f] for f in batch], [rates[f] for f in batch], grid, Q, pi_root,
-                                device=device) as fit:
+        with inp.fitter(batch, [inp.trees[f] for f in batch]) as fit:
             t_create = time.time() - st
             live = np.ones(len(batch), dtype=bool)
             ms_pass = ms_mstep = 0.0
@@ -373,24 +413,27 @@ def ml_branch_lengths(tree_dir: str, msa_dir: str, site_rates_dir: str, families
             _, fam_final = fit.log_likelihoods()
         for k, f in enumerate(batch):
             logs[f].append(f"final {float(fam_final[k])!r}\n")
-            t = Tree()
-            t.add_nodes(trees[f].nodes())
-            t.add_edges([(u, v, lengths[k][v]) for u, v, _ in trees[f].edges()])
-            out_trees[f] = t
+            out_trees[f] = _tree_at(inp.trees[f], lengths[k])
             profs[f] = dict(create_time=t_create / len(batch), rounds=rounds, passes_kernel_ms=ms_pass / len(batch),
                             mstep_kernel_ms=ms_mstep / len(batch), fit_time=(time.time() - st) / len(batch))   # (shares of the batch)
-    st = time.time()
-    lls = dp_likelihood_computation_batch(out_trees, msas, [None] * len(families), [[float(x) for x in r] for r in rates], alphabet,
-                                          pi_root, Q, device=device)
-    t_ll = (time.time() - st) / max(len(families), 1)
-    t_total = (time.time() - st_all) / max(len(families), 1)
-    for f, family in enumerate(families):
-        write_tree(out_trees[f], os.path.join(output_tree_dir, family + ".txt"))
-        with open(os.path.join(output_tree_dir, family + ".rounds"), "w") as fh:
-            fh.write("".join(logs[f]))
-        write_log_likelihood(lls[f], os.path.join(output_likelihood_dir, family + ".txt"))
-        with open(os.path.join(output_tree_dir, family + ".profiling"), "w") as fh:
-            fh.write("".join(f"{k}: {v}\n" for k, v in profs[f].items()) + f"likelihood_time: {t_ll}\ntotal_time: {t_total}")
+    _write_stage_outputs(inp, out_trees, logs, ".rounds", profs)
+
+
+def _nj_stage(output_tree_dir: Optional[str], output_site_rates_dir: Optional[str], output_likelihood_dir: Optional[str],
+              **nj_args) -> Dict[str, str]:
+    """`nj_trees(**nj_args)` as the first stage of `nj_ml_trees`, `nj_nni_trees` and `nj_spr_trees` -> its output directories.
+    With a cache directory its trees and likelihoods go to the cache; without one the three output directories are required
+    and they go to the `nj_trees` subdirectories of the estimator's."""
+    from ..caching import get_cache_dir
+    from ._nj import nj_trees
+    nj_out = dict(output_tree_dir=None, output_site_rates_dir=output_site_rates_dir, output_likelihood_dir=None)
+    if get_cache_dir() is None:
+        if output_tree_dir is None or output_site_rates_dir is None or output_likelihood_dir is None:
+            raise ValueError("output_tree_dir, output_site_rates_dir and output_likelihood_dir are required without a cache directory")
+        nj_out.update(output_tree_dir=os.path.join(output_tree_dir, "nj_trees"),
+                      output_likelihood_dir=os.path.join(output_likelihood_dir, "nj_trees"))
+    nj = nj_trees(**nj_args, **nj_out)
+    return nj if nj is not None else nj_out
 
 
 def nj_ml_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, num_rate_categories: int, max_iters: int = 50,
@@ -404,20 +447,11 @@ def nj_ml_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, num
     `nj_trees`' own.  Both stages are cached on their own; `nj_trees`, its files and its cache keys are what they are without
     this function.  With no cache directory the three output directories are required and the neighbour-joining trees and
     likelihoods go to their `nj_trees` subdirectories."""
-    from ..caching import get_cache_dir
-    from ._nj import nj_trees
-    nj_out = dict(output_tree_dir=None, output_site_rates_dir=output_site_rates_dir, output_likelihood_dir=None)
-    if get_cache_dir() is None:
-        if output_tree_dir is None or output_site_rates_dir is None or output_likelihood_dir is None:
-            raise ValueError("output_tree_dir, output_site_rates_dir and output_likelihood_dir are required without a cache directory")
-        nj_out.update(output_tree_dir=os.path.join(output_tree_dir, "nj_trees"),
-                      output_likelihood_dir=os.path.join(output_likelihood_dir, "nj_trees"))
     grid_args = dict(quantization_grid_center=quantization_grid_center, quantization_grid_step=quantization_grid_step,
                      quantization_grid_num_steps=quantization_grid_num_steps)
-    nj = nj_trees(msa_dir=msa_dir, families=families, rate_matrix_path=rate_matrix_path, num_rate_categories=num_rate_categories,
-                  max_iters=max_iters, num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, joiner=joiner, **grid_args,
-                  **nj_out)
-    nj = nj if nj is not None else nj_out
+    nj = _nj_stage(output_tree_dir, output_site_rates_dir, output_likelihood_dir, msa_dir=msa_dir, families=families,
+                   rate_matrix_path=rate_matrix_path, num_rate_categories=num_rate_categories, max_iters=max_iters,
+                   num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, joiner=joiner, **grid_args)
     ml_out = dict(output_tree_dir=output_tree_dir, output_likelihood_dir=output_likelihood_dir)
     ml = ml_branch_lengths(tree_dir=nj["output_tree_dir"], msa_dir=msa_dir, site_rates_dir=nj["output_site_rates_dir"],
                            families=families, rate_matrix_path=rate_matrix_path, num_rounds=num_rounds, **grid_args, **ml_out)

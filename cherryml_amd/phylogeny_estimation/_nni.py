@@ -18,9 +18,9 @@ import numpy as np
 
 from .. import _lib
 from ..caching import cached_computation
-from ..io._tree import Tree, read_tree, write_tree
-from ._fast_cherries import quantization_points_ble
-from ._ml_lengths import DEFAULT_MAX_BANK_BYTES, BranchLengthFitter, _batches
+from ..io._tree import Tree
+from ._ml_lengths import DEFAULT_MAX_BANK_BYTES, _nj_stage
+from ._search import HandleHooks, MoveKind, search_trees
 
 
 def enumerate_nni_moves(parent) -> np.ndarray:
@@ -95,6 +95,94 @@ def select_nni(moves, delta, parent, min_gain: float = 0.0) -> np.ndarray:
     return np.array(taken, dtype=np.int64)
 
 
+def _scan_nni(fit, trees, want):
+    moves, delta = fit.nni_scan([m if w else m[:0] for m, w in zip(fit.nni_moves(), want)])
+    return moves, delta, fit.last_nni_kernel_ms[1]
+
+
+NNI = MoveKind(stage="ml_nni_trees", log_ext=".nni", rounds_key="nni_rounds", scan=_scan_nni, select=select_nni,
+               apply=lambda tree, moves, grid: apply_nni(tree, moves))
+
+
+class _SupportsAndBootstrap(HandleHooks):
+    """`ml_nni_trees`' `output_support_dir` and `output_bootstrap_dir`, either or none, on the search's own handles"""
+
+    def __init__(self, families: List[str], output_support_dir: Optional[str], num_support_replicates: int,
+                 output_bootstrap_dir: Optional[str], num_bootstrap_replicates: int, bootstrap_seed: int, max_bank_bytes: int):
+        self.families, self.max_bank_bytes = families, max_bank_bytes
+        self.support_dir, self.n_support = output_support_dir, num_support_replicates
+        self.bootstrap_dir, self.n_boot, self.bootstrap_seed = output_bootstrap_dir, int(num_bootstrap_replicates), bootstrap_seed
+        F, n_boot = len(families), max(self.n_boot, 0)
+        self.supports: List[Optional[tuple]] = [None] * F   # the final trees' supports
+        # per family: the running best score of every replicate, the (t, code) it chose, the contributing trees and per
+        # contribution its NNI round and its number of candidates
+        self.best: List[Optional[np.ndarray]] = [None] * F
+        self.choice = [(np.full(n_boot, -1, dtype=np.int64), np.full(n_boot, -2, dtype=np.int64)) for _ in families]
+        self.contributions: List[List[Tree]] = [[] for _ in families]
+        self.rounds: List[List[int]] = [[] for _ in families]
+        self.cands: List[List[int]] = [[] for _ in families]
+        self.ufb = self.all_moves = None                    # of the current handle
+
+    def on_handle(self, fit, fams, go, ends, prof) -> None:
+        from ._supports import support_seeds
+        names = [self.families[f] for f in fams]
+        if self.support_dir is not None and any(ends):
+            sup = fit.branch_supports(self.n_support, seeds=support_seeds(names, 0),
+                                      moves=[m if e else m[:0] for m, e in zip(fit.nni_moves(), ends)])
+            for k, f in enumerate(fams):
+                if ends[k]:
+                    self.supports[f] = sup[k]
+        self.ufb = None
+        if self.bootstrap_dir is not None and go.any():
+            # every family whose tree on this handle is accepted contributes it and all its neighbours; a refused
+            # candidate meets an incoming best of +inf, which nothing beats, and its result is dropped
+            n_boot = self.n_boot
+            self.all_moves = fit.nni_moves()
+            st_ufb = time.time()
+            self.ufb = fit.bootstrap_best(n_boot, seeds=support_seeds(names, self.bootstrap_seed),
+                                          best=[(np.full(n_boot, -np.inf) if self.best[f] is None else self.best[f]) if go[k]
+                                                else np.full(n_boot, np.inf) for k, f in enumerate(fams)],
+                                          moves=[m if g else m[:0] for m, g in zip(self.all_moves, go)])
+            for f in fams:                             # (shares of the batch; these keys exist only with the bootstrap)
+                prof[f]["bootstrap_time"] = prof[f].get("bootstrap_time", 0.0) + (time.time() - st_ufb) / len(fams)
+                prof[f]["bootstrap_kernel_ms"] = (prof[f].get("bootstrap_kernel_ms", 0.0)
+                                                  + fit.last_ufboot_kernel_ms[2] / len(fams))
+                prof[f]["bootstrap_scan_kernel_ms"] = (prof[f].get("bootstrap_scan_kernel_ms", 0.0)   # its own passes and scan
+                                                       + sum(fit.last_ufboot_kernel_ms[:2]) / len(fams))
+
+    def on_accepted(self, k, f, tree, rnd) -> None:
+        from ._ufboot import update_choice
+        if self.ufb is not None:
+            self.best[f] = self.ufb[k][0]
+            update_choice(self.choice[f], len(self.contributions[f]), self.ufb[k][1])
+            self.contributions[f].append(tree)
+            self.rounds[f].append(rnd)
+            self.cands[f].append(1 + len(self.all_moves[k]))
+
+    def finish(self, inp, trees) -> None:
+        from ._supports import support_seeds, supports_of_trees, write_supports
+        from ._ufboot import choices_lines, ufboot_supports, write_ufboot_supports
+        if self.support_dir is not None:
+            os.makedirs(self.support_dir, exist_ok=True)
+            # a family whose last candidate was refused ends on the tree of an earlier handle: one more handle for those
+            rest = [f for f in range(len(trees)) if self.supports[f] is None]
+            if rest:
+                got, _ = supports_of_trees([trees[f] for f in rest], [inp.codes[f] for f in rest], [inp.rates[f] for f in rest],
+                                           inp.grid, inp.Q, inp.pi_root, support_seeds([self.families[f] for f in rest], 0),
+                                           int(self.n_support), inp.device, self.max_bank_bytes)
+                for f, res in zip(rest, got):
+                    self.supports[f] = res
+            for f, family in enumerate(self.families):
+                write_supports(os.path.join(self.support_dir, family + ".txt"), list(trees[f].nodes()), self.supports[f])
+        if self.bootstrap_dir is not None:
+            os.makedirs(self.bootstrap_dir, exist_ok=True)
+            for f, family in enumerate(self.families):
+                nodes, share = ufboot_supports(trees[f], self.contributions[f], self.choice[f])
+                write_ufboot_supports(os.path.join(self.bootstrap_dir, family + ".txt"), list(trees[f].nodes()), nodes, share)
+                with open(os.path.join(self.bootstrap_dir, family + ".choices"), "w") as fh:
+                    fh.write("".join(choices_lines(self.rounds[f], self.cands[f], self.choice[f])))
+
+
 @cached_computation(output_dirs=["output_tree_dir", "output_likelihood_dir"], exclude_args=["max_bank_bytes"])
 def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: List[str], rate_matrix_path: str,
                  num_nni_rounds: int = 10, num_rounds: int = 10, quantization_grid_center: float = 0.03,
@@ -127,188 +215,11 @@ def ml_nni_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: Lis
     best tree has the split of the edge above it, `<family>.choices` per contributing handle
     `<t> <nni_round> <candidates> <replicates won by the tree> <replicates won by its neighbours>`.  A family's file does not
     depend on its batch; without the directory (the default) every other file is byte for byte what it is with it."""
-    from ..counting._host import read_msa, read_site_rates
-    from ..counting._stage import _device_index
-    from ..evaluation._likelihood import (_family_units, _stationary_distribution, dp_likelihood_computation_batch,
-                                          write_log_likelihood)
-    from ..io import read_rate_matrix
-    from ._supports import support_seeds, supports_of_trees, write_supports
-    from ._ufboot import choices_lines, ufboot_supports, update_choice, write_ufboot_supports
-    if output_tree_dir is None or output_likelihood_dir is None:
-        raise ValueError("output_tree_dir and output_likelihood_dir are required")
-    if _lib.load().cb_device_count() <= 0:
-        raise _lib.CherryBankError("ml_nni_trees: no HIP device visible; the search runs on the MI355X only (no CPU fallback)")
-    st_all = time.time()
-    for d in (output_tree_dir, output_likelihood_dir):
-        os.makedirs(d, exist_ok=True)
-    rm = read_rate_matrix(rate_matrix_path)
-    alphabet = [str(c) for c in rm.columns]
-    Q = np.ascontiguousarray(rm.to_numpy(), dtype=np.float64)
-    pi_root = _stationary_distribution(Q)
-    grid = np.array(quantization_points_ble(quantization_grid_center, quantization_grid_step, quantization_grid_num_steps))
-    device = _device_index()
-    trees, msas, rates, codes = [], [], [], []
-    for family in families:
-        tree = read_tree(os.path.join(tree_dir, family + ".txt"))
-        msa = read_msa(os.path.join(msa_dir, family + ".txt"))
-        r = np.asarray(read_site_rates(os.path.join(site_rates_dir, family + ".txt")), dtype=np.float64)
-        trees.append(tree), msas.append(msa), rates.append(r)
-        # (the codes' rows follow tree.nodes(), which no move changes)
-        codes.append(_family_units(tree, msa, None, len(r), alphabet, False)[2])
-    F = len(families)
-    logs: List[List[str]] = [[] for _ in families]
-    prof = [dict(create_time=0.0, scan_time=0.0, scan_kernel_ms=0.0, fit_time=0.0, handles=0, nni_rounds=0, moves_applied=0)
-            for _ in families]
-    final_ll: List[Optional[float]] = [None] * F
-    supports: List[Optional[tuple]] = [None] * F   # (with output_support_dir) the final trees' supports
-    # (with output_bootstrap_dir) per family: the running best score of every replicate, the (t, code) it chose, the contributing
-    # trees and per contribution its NNI round and its number of candidates
-    n_boot = int(num_bootstrap_replicates)
-    ufb_best: List[Optional[np.ndarray]] = [None] * F
-    ufb_choice = [(np.full(max(n_boot, 0), -1, dtype=np.int64), np.full(max(n_boot, 0), -2, dtype=np.int64)) for _ in families]
-    contributions: List[List[Tree]] = [[] for _ in families]
-    ufb_rounds: List[List[int]] = [[] for _ in families]
-    ufb_cands: List[List[int]] = [[] for _ in families]
-    bank_bytes = [2 * grid.size * np.unique(r).size * Q.size * 8 for r in rates]
-    # Per family: rnd = its NNI round; trees[f] = the tree the next handle takes -- the input, or a candidate (fitted[f] with the
-    # moves sel[f] applied) that has to beat before[f].  ONE handle per pass over the work list: on a candidate its
-    # log_likelihoods() before any EM round decides (the lengths are the fitted ones: grid points snap to themselves), and the
-    # accepted families go on in the same handle with the EM rounds and the scan of their next round.
-    rnd = [0] * F
-    before: List[Optional[float]] = [None] * F
-    fitted: List[Optional[Tree]] = [None] * F
-    sel: List[Optional[np.ndarray]] = [None] * F
-    scanned, selected = [0] * F, [0] * F
-    work = list(range(F))
-    while work:
-        nxt: List[int] = []
-        for batch in _batches([bank_bytes[f] for f in work], int(max_bank_bytes)):
-            fams = [work[k] for k in batch]
-            st = time.time()
-            with BranchLengthFitter([trees[f] for f in fams], [codes[f] for f in fams], [rates[f] for f in fams], grid, Q, pi_root,
-                                    device=device) as fit:
-                t_create = time.time() - st
-                go = np.ones(len(fams), dtype=bool)            # the input tree, or an accepted candidate
-                if any(before[f] is not None for f in fams):
-                    _, ll0 = fit.log_likelihoods()
-                    for k, f in enumerate(fams):
-                        if before[f] is None:
-                            continue
-                        if ll0[k] > before[f]:
-                            logs[f].append(f"{rnd[f]} {before[f]!r} {scanned[f]} {selected[f]} {len(sel[f])} {float(ll0[k])!r}\n")
-                            prof[f]["moves_applied"] += len(sel[f])
-                            rnd[f] += 1
-                        else:
-                            go[k] = False
-                live = go.copy()                               # (a refused candidate's rounds are nobody's)
-                for _ in range(int(num_rounds)):
-                    if not live.any():
-                        break
-                    n_changed, _ = fit.round()
-                    live &= n_changed > 0
-                lengths = fit.lengths()
-                _, fam_ll = fit.log_likelihoods()
-                want = [bool(go[k]) and rnd[f] < int(num_nni_rounds) for k, f in enumerate(fams)]
-                st_scan = time.time()
-                if any(want):
-                    moves, delta = fit.nni_scan([m if w else m[:0] for m, w in zip(fit.nni_moves(), want)])
-                t_scan, ms_scan = time.time() - st_scan, fit.last_nni_kernel_ms[1]
-                picked = [moves[k][select_nni(moves[k], delta[k], _parent_array(trees[f]))] if want[k] else None
-                          for k, f in enumerate(fams)]
-                if output_support_dir is not None:
-                    # the families that end on this handle's tree at these lengths: no further round, or no move that gains
-                    ends = [bool(go[k]) and (not want[k] or len(picked[k]) == 0) for k in range(len(fams))]
-                    if any(ends):
-                        sup = fit.branch_supports(num_support_replicates, seeds=support_seeds([families[f] for f in fams], 0),
-                                                  moves=[m if e else m[:0] for m, e in zip(fit.nni_moves(), ends)])
-                        for k, f in enumerate(fams):
-                            if ends[k]:
-                                supports[f] = sup[k]
-                ufb = None
-                if output_bootstrap_dir is not None and go.any():
-                    # every family whose tree on this handle is accepted contributes it and all its neighbours; a refused
-                    # candidate meets an incoming best of +inf, which nothing beats, and its result is dropped
-                    all_moves = fit.nni_moves()
-                    st_ufb = time.time()
-                    ufb = fit.bootstrap_best(n_boot, seeds=support_seeds([families[f] for f in fams], bootstrap_seed),
-                                             best=[(np.full(n_boot, -np.inf) if ufb_best[f] is None else ufb_best[f]) if go[k]
-                                                   else np.full(n_boot, np.inf) for k, f in enumerate(fams)],
-                                             moves=[m if g else m[:0] for m, g in zip(all_moves, go)])
-                    for f in fams:                             # (shares of the batch; these keys exist only with the bootstrap)
-                        prof[f]["bootstrap_time"] = prof[f].get("bootstrap_time", 0.0) + (time.time() - st_ufb) / len(fams)
-                        prof[f]["bootstrap_kernel_ms"] = (prof[f].get("bootstrap_kernel_ms", 0.0)
-                                                          + fit.last_ufboot_kernel_ms[2] / len(fams))
-                        prof[f]["bootstrap_scan_kernel_ms"] = (prof[f].get("bootstrap_scan_kernel_ms", 0.0)   # its own passes and scan
-                                                               + sum(fit.last_ufboot_kernel_ms[:2]) / len(fams))
-            for k, f in enumerate(fams):
-                for key, x in (("create_time", t_create), ("scan_time", t_scan), ("scan_kernel_ms", ms_scan),
-                               ("fit_time", time.time() - st)):
-                    prof[f][key] += x / len(fams)              # (shares of the batch)
-                prof[f]["handles"] += 1
-                if not go[k]:                                  # refused: half of the moves, down to one, whose gain is exact
-                    if len(sel[f]) > 1:
-                        sel[f] = sel[f][:len(sel[f]) // 2]
-                        trees[f] = apply_nni(fitted[f], sel[f])
-                        nxt.append(f)
-                    else:                                      # (rounding only)
-                        logs[f].append(f"{rnd[f]} {before[f]!r} {scanned[f]} {selected[f]} 0 {before[f]!r}\n")
-                        trees[f], final_ll[f] = fitted[f], before[f]
-                    continue
-                t = Tree()
-                t.add_nodes(trees[f].nodes())
-                t.add_edges([(u, v, lengths[k][v]) for u, v, _ in trees[f].edges()])
-                trees[f], ll = t, float(fam_ll[k])
-                if ufb is not None:
-                    ufb_best[f] = ufb[k][0]
-                    update_choice(ufb_choice[f], len(contributions[f]), ufb[k][1])
-                    contributions[f].append(t)
-                    ufb_rounds[f].append(rnd[f])
-                    ufb_cands[f].append(1 + len(all_moves[k]))
-                if not want[k]:                                # the topology of the last round's moves after its own EM rounds
-                    final_ll[f] = ll
-                    continue
-                prof[f]["nni_rounds"] += 1
-                s = picked[k]
-                scanned[f], selected[f] = len(moves[k]), len(s)
-                if len(s) == 0:                                # no move gains: finished
-                    logs[f].append(f"{rnd[f]} {ll!r} {scanned[f]} 0 0 {ll!r}\n")
-                    final_ll[f] = ll
-                    continue
-                fitted[f], before[f], sel[f] = t, ll, s
-                trees[f] = apply_nni(t, s)
-                nxt.append(f)
-        work = nxt
-    if output_support_dir is not None:
-        os.makedirs(output_support_dir, exist_ok=True)
-        # a family whose last candidate was refused ends on the tree of an earlier handle: one more handle for those
-        rest = [f for f in range(F) if supports[f] is None]
-        if rest:
-            got, _ = supports_of_trees([trees[f] for f in rest], [codes[f] for f in rest], [rates[f] for f in rest], grid, Q, pi_root,
-                                       support_seeds([families[f] for f in rest], 0), int(num_support_replicates), device,
-                                       max_bank_bytes)
-            for f, res in zip(rest, got):
-                supports[f] = res
-        for f, family in enumerate(families):
-            write_supports(os.path.join(output_support_dir, family + ".txt"), list(trees[f].nodes()), supports[f])
-    if output_bootstrap_dir is not None:
-        os.makedirs(output_bootstrap_dir, exist_ok=True)
-        for f, family in enumerate(families):
-            nodes, share = ufboot_supports(trees[f], contributions[f], ufb_choice[f])
-            write_ufboot_supports(os.path.join(output_bootstrap_dir, family + ".txt"), list(trees[f].nodes()), nodes, share)
-            with open(os.path.join(output_bootstrap_dir, family + ".choices"), "w") as fh:
-                fh.write("".join(choices_lines(ufb_rounds[f], ufb_cands[f], ufb_choice[f])))
-    st = time.time()
-    lls = dp_likelihood_computation_batch(trees, msas, [None] * F, [[float(x) for x in r] for r in rates], alphabet, pi_root, Q,
-                                          device=device)
-    t_ll = (time.time() - st) / max(F, 1)
-    t_total = (time.time() - st_all) / max(F, 1)
-    for f, family in enumerate(families):
-        write_tree(trees[f], os.path.join(output_tree_dir, family + ".txt"))
-        with open(os.path.join(output_tree_dir, family + ".nni"), "w") as fh:
-            fh.write("".join(logs[f]) + f"final {final_ll[f]!r}\n")
-        write_log_likelihood(lls[f], os.path.join(output_likelihood_dir, family + ".txt"))
-        with open(os.path.join(output_tree_dir, family + ".profiling"), "w") as fh:
-            fh.write("".join(f"{k}: {v}\n" for k, v in prof[f].items()) + f"likelihood_time: {t_ll}\ntotal_time: {t_total}")
+    hooks = _SupportsAndBootstrap(families, output_support_dir, num_support_replicates, output_bootstrap_dir,
+                                  num_bootstrap_replicates, bootstrap_seed, max_bank_bytes)
+    search_trees(NNI, num_nni_rounds, num_rounds, max_bank_bytes, hooks, tree_dir, msa_dir, site_rates_dir, families,
+                 rate_matrix_path, (quantization_grid_center, quantization_grid_step, quantization_grid_num_steps), output_tree_dir,
+                 output_likelihood_dir)
 
 
 def nj_nni_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, num_rate_categories: int, max_iters: int = 50,
@@ -326,22 +237,13 @@ def nj_nni_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, nu
     `output_support_dir` the supports of the final trees are written there (`ml_nni_trees`); the returned dict is the same.
     With `output_bootstrap_dir` the bootstrap supports from the search's own trees are written there (`ml_nni_trees`,
     `num_bootstrap_replicates`, `bootstrap_seed`); the returned dict is the same."""
-    from ..caching import get_cache_dir
-    from ._nj import nj_trees
     if _lib.load().cb_device_count() <= 0:
         raise _lib.CherryBankError("nj_nni_trees: no HIP device visible; the search runs on the MI355X only (no CPU fallback)")
-    nj_out = dict(output_tree_dir=None, output_site_rates_dir=output_site_rates_dir, output_likelihood_dir=None)
-    if get_cache_dir() is None:
-        if output_tree_dir is None or output_site_rates_dir is None or output_likelihood_dir is None:
-            raise ValueError("output_tree_dir, output_site_rates_dir and output_likelihood_dir are required without a cache directory")
-        nj_out.update(output_tree_dir=os.path.join(output_tree_dir, "nj_trees"),
-                      output_likelihood_dir=os.path.join(output_likelihood_dir, "nj_trees"))
     grid_args = dict(quantization_grid_center=quantization_grid_center, quantization_grid_step=quantization_grid_step,
                      quantization_grid_num_steps=quantization_grid_num_steps)
-    nj = nj_trees(msa_dir=msa_dir, families=families, rate_matrix_path=rate_matrix_path, num_rate_categories=num_rate_categories,
-                  max_iters=max_iters, num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, joiner=joiner, **grid_args,
-                  **nj_out)
-    nj = nj if nj is not None else nj_out
+    nj = _nj_stage(output_tree_dir, output_site_rates_dir, output_likelihood_dir, msa_dir=msa_dir, families=families,
+                   rate_matrix_path=rate_matrix_path, num_rate_categories=num_rate_categories, max_iters=max_iters,
+                   num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, joiner=joiner, **grid_args)
     out = dict(output_tree_dir=output_tree_dir, output_likelihood_dir=output_likelihood_dir)
     sup = dict(output_support_dir=output_support_dir, num_support_replicates=num_support_replicates,
                output_bootstrap_dir=output_bootstrap_dir, num_bootstrap_replicates=num_bootstrap_replicates,

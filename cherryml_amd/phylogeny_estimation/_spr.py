@@ -18,17 +18,16 @@ higher.  `nj_spr_trees` is the tree estimator `nj_trees` + `ml_spr_trees` (+ `ml
 Out of scope: TBR, optimising the three lengths per candidate beyond the one offered triple, changing a handle's topology in
 place, S > 32, SPR candidates in `bootstrap_best` and `branch_supports`."""
 import os
-import time
 from typing import Dict, List, Optional, Set, Tuple
 
 import numpy as np
 
 from .. import _lib
 from ..caching import cached_computation
-from ..io._tree import Tree, read_tree, write_tree
-from ._fast_cherries import quantization_points_ble
-from ._ml_lengths import DEFAULT_MAX_BANK_BYTES, BranchLengthFitter, _batches
+from ..io._tree import Tree
+from ._ml_lengths import DEFAULT_MAX_BANK_BYTES, _nj_stage
 from ._nni import _parent_array
+from ._search import MoveKind, search_trees
 
 SPR_MAX_RADIUS = 8   # CB_SPR_MAX_RADIUS of include/cherrybank.h
 
@@ -215,129 +214,16 @@ def ml_spr_trees(tree_dir: str, msa_dir: str, site_rates_dir: str, families: Lis
     `<family>.spr` (per round `<round> <log-likelihood before> <moves scanned> <selected> <applied> <log-likelihood after,
     carried lengths>`, then `final <log-likelihood of the written tree>`: no number is below the one before it),
     `<family>.profiling`, and `<output_likelihood_dir>/<family>.txt` as `ml_branch_lengths` writes it."""
-    from ..counting._host import read_msa, read_site_rates
-    from ..counting._stage import _device_index
-    from ..evaluation._likelihood import (_family_units, _stationary_distribution, dp_likelihood_computation_batch,
-                                          write_log_likelihood)
-    from ..io import read_rate_matrix
-    if output_tree_dir is None or output_likelihood_dir is None:
-        raise ValueError("output_tree_dir and output_likelihood_dir are required")
-    if _lib.load().cb_device_count() <= 0:
-        raise _lib.CherryBankError("ml_spr_trees: no HIP device visible; the search runs on the MI355X only (no CPU fallback)")
-    st_all = time.time()
-    for d in (output_tree_dir, output_likelihood_dir):
-        os.makedirs(d, exist_ok=True)
-    rm = read_rate_matrix(rate_matrix_path)
-    alphabet = [str(c) for c in rm.columns]
-    Q = np.ascontiguousarray(rm.to_numpy(), dtype=np.float64)
-    pi_root = _stationary_distribution(Q)
-    grid = np.array(quantization_points_ble(quantization_grid_center, quantization_grid_step, quantization_grid_num_steps))
-    device = _device_index()
-    trees, msas, rates, codes = [], [], [], []
-    for family in families:
-        tree = read_tree(os.path.join(tree_dir, family + ".txt"))
-        msa = read_msa(os.path.join(msa_dir, family + ".txt"))
-        r = np.asarray(read_site_rates(os.path.join(site_rates_dir, family + ".txt")), dtype=np.float64)
-        trees.append(tree), msas.append(msa), rates.append(r)
-        # (the codes' rows follow tree.nodes(), which no move changes)
-        codes.append(_family_units(tree, msa, None, len(r), alphabet, False)[2])
-    F = len(families)
-    logs: List[List[str]] = [[] for _ in families]
-    prof = [dict(create_time=0.0, scan_time=0.0, scan_kernel_ms=0.0, fit_time=0.0, handles=0, spr_rounds=0, moves_applied=0)
-            for _ in families]
-    final_ll: List[Optional[float]] = [None] * F
-    bank_bytes = [2 * grid.size * np.unique(r).size * Q.size * 8 for r in rates]
-    # ml_nni_trees' bookkeeping: trees[f] = the tree the next handle takes -- the input, or a candidate (fitted[f] with the moves
-    # sel[f] applied) that has to beat before[f]; ONE handle per pass over the work list
-    rnd = [0] * F
-    before: List[Optional[float]] = [None] * F
-    fitted: List[Optional[Tree]] = [None] * F
-    sel: List[Optional[np.ndarray]] = [None] * F
-    scanned, selected = [0] * F, [0] * F
-    work = list(range(F))
-    while work:
-        nxt: List[int] = []
-        for batch in _batches([bank_bytes[f] for f in work], int(max_bank_bytes)):
-            fams = [work[k] for k in batch]
-            st = time.time()
-            with BranchLengthFitter([trees[f] for f in fams], [codes[f] for f in fams], [rates[f] for f in fams], grid, Q, pi_root,
-                                    device=device) as fit:
-                t_create = time.time() - st
-                go = np.ones(len(fams), dtype=bool)            # the input tree, or an accepted candidate
-                if any(before[f] is not None for f in fams):
-                    _, ll0 = fit.log_likelihoods()
-                    for k, f in enumerate(fams):
-                        if before[f] is None:
-                            continue
-                        if ll0[k] > before[f]:
-                            logs[f].append(f"{rnd[f]} {before[f]!r} {scanned[f]} {selected[f]} {len(sel[f])} {float(ll0[k])!r}\n")
-                            prof[f]["moves_applied"] += len(sel[f])
-                            rnd[f] += 1
-                        else:
-                            go[k] = False
-                live = go.copy()                               # (a refused candidate's rounds are nobody's)
-                for _ in range(int(num_rounds)):
-                    if not live.any():
-                        break
-                    n_changed, _ = fit.round()
-                    live &= n_changed > 0
-                lengths = fit.lengths()
-                _, fam_ll = fit.log_likelihoods()
-                want = [bool(go[k]) and rnd[f] < int(num_spr_rounds) for k, f in enumerate(fams)]
-                st_scan = time.time()
-                ms_scan = 0.0
-                if any(want):
-                    none = np.zeros((0, 5), dtype=np.int32)
-                    moves, delta = fit.spr_scan([_moves_at(_parent_array(trees[f]), tau, grid, spr_radius) if w else none
-                                                 for f, tau, w in zip(fams, fit.indices(), want)])
-                    ms_scan = fit.last_spr_kernel_ms[1]
-                t_scan = time.time() - st_scan
-                picked = [moves[k][select_spr(moves[k], delta[k], _parent_array(trees[f]))] if want[k] else None
-                          for k, f in enumerate(fams)]
-            for k, f in enumerate(fams):
-                for key, x in (("create_time", t_create), ("scan_time", t_scan), ("scan_kernel_ms", ms_scan),
-                               ("fit_time", time.time() - st)):
-                    prof[f][key] += x / len(fams)              # (shares of the batch)
-                prof[f]["handles"] += 1
-                if not go[k]:                                  # refused: half of the moves, down to one, whose gain is exact
-                    if len(sel[f]) > 1:
-                        sel[f] = sel[f][:len(sel[f]) // 2]
-                        trees[f] = apply_spr(fitted[f], sel[f], grid)
-                        nxt.append(f)
-                    else:                                      # (rounding only)
-                        logs[f].append(f"{rnd[f]} {before[f]!r} {scanned[f]} {selected[f]} 0 {before[f]!r}\n")
-                        trees[f], final_ll[f] = fitted[f], before[f]
-                    continue
-                t = Tree()
-                t.add_nodes(trees[f].nodes())
-                t.add_edges([(u, v, lengths[k][v]) for u, v, _ in trees[f].edges()])
-                trees[f], ll = t, float(fam_ll[k])
-                if not want[k]:                                # the topology of the last round's moves after its own EM rounds
-                    final_ll[f] = ll
-                    continue
-                prof[f]["spr_rounds"] += 1
-                s = picked[k]
-                scanned[f], selected[f] = len(moves[k]), len(s)
-                if len(s) == 0:                                # no move gains: finished
-                    logs[f].append(f"{rnd[f]} {ll!r} {scanned[f]} 0 0 {ll!r}\n")
-                    final_ll[f] = ll
-                    continue
-                fitted[f], before[f], sel[f] = t, ll, s
-                trees[f] = apply_spr(t, s, grid)
-                nxt.append(f)
-        work = nxt
-    st = time.time()
-    lls = dp_likelihood_computation_batch(trees, msas, [None] * F, [[float(x) for x in r] for r in rates], alphabet, pi_root, Q,
-                                          device=device)
-    t_ll = (time.time() - st) / max(F, 1)
-    t_total = (time.time() - st_all) / max(F, 1)
-    for f, family in enumerate(families):
-        write_tree(trees[f], os.path.join(output_tree_dir, family + ".txt"))
-        with open(os.path.join(output_tree_dir, family + ".spr"), "w") as fh:
-            fh.write("".join(logs[f]) + f"final {final_ll[f]!r}\n")
-        write_log_likelihood(lls[f], os.path.join(output_likelihood_dir, family + ".txt"))
-        with open(os.path.join(output_tree_dir, family + ".profiling"), "w") as fh:
-            fh.write("".join(f"{k}: {v}\n" for k, v in prof[f].items()) + f"likelihood_time: {t_ll}\ntotal_time: {t_total}")
+    def scan(fit, trees, want):
+        none = np.zeros((0, 5), dtype=np.int32)
+        moves, delta = fit.spr_scan([_moves_at(_parent_array(tree), tau, fit.grid, spr_radius) if w else none
+                                     for tree, tau, w in zip(trees, fit.indices(), want)])
+        return moves, delta, fit.last_spr_kernel_ms[1]
+
+    kind = MoveKind(stage="ml_spr_trees", log_ext=".spr", rounds_key="spr_rounds", scan=scan, select=select_spr, apply=apply_spr)
+    search_trees(kind, num_spr_rounds, num_rounds, max_bank_bytes, None, tree_dir, msa_dir, site_rates_dir, families,
+                 rate_matrix_path, (quantization_grid_center, quantization_grid_step, quantization_grid_num_steps), output_tree_dir,
+                 output_likelihood_dir)
 
 
 def nj_spr_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, num_rate_categories: int, max_iters: int = 50,
@@ -357,30 +243,22 @@ def nj_spr_trees(*, msa_dir: str, families: List[str], rate_matrix_path: str, nu
     `ml_nni_trees` follows, the SPR search's to their `spr_trees` subdirectories.  The supports and the search bootstrap are
     `ml_nni_trees`' (the SPR search has none): `output_support_dir` and `output_bootstrap_dir` need `num_nni_rounds` > 0."""
     from ..caching import get_cache_dir
-    from ._nj import nj_trees
     from ._nni import ml_nni_trees
     if _lib.load().cb_device_count() <= 0:
         raise _lib.CherryBankError("nj_spr_trees: no HIP device visible; the search runs on the MI355X only (no CPU fallback)")
     nni = int(num_nni_rounds) > 0
     if not nni and (output_support_dir is not None or output_bootstrap_dir is not None):
         raise ValueError("nj_spr_trees: output_support_dir and output_bootstrap_dir are ml_nni_trees' (num_nni_rounds > 0)")
-    nj_out = dict(output_tree_dir=None, output_site_rates_dir=output_site_rates_dir, output_likelihood_dir=None)
     out = dict(output_tree_dir=output_tree_dir, output_likelihood_dir=output_likelihood_dir)
     spr_out = dict(out) if not nni else dict(output_tree_dir=None, output_likelihood_dir=None)
-    if get_cache_dir() is None:
-        if output_tree_dir is None or output_site_rates_dir is None or output_likelihood_dir is None:
-            raise ValueError("output_tree_dir, output_site_rates_dir and output_likelihood_dir are required without a cache directory")
-        nj_out.update(output_tree_dir=os.path.join(output_tree_dir, "nj_trees"),
-                      output_likelihood_dir=os.path.join(output_likelihood_dir, "nj_trees"))
-        if nni:
-            spr_out.update(output_tree_dir=os.path.join(output_tree_dir, "spr_trees"),
-                           output_likelihood_dir=os.path.join(output_likelihood_dir, "spr_trees"))
     grid_args = dict(quantization_grid_center=quantization_grid_center, quantization_grid_step=quantization_grid_step,
                      quantization_grid_num_steps=quantization_grid_num_steps)
-    nj = nj_trees(msa_dir=msa_dir, families=families, rate_matrix_path=rate_matrix_path, num_rate_categories=num_rate_categories,
-                  max_iters=max_iters, num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, joiner=joiner, **grid_args,
-                  **nj_out)
-    nj = nj if nj is not None else nj_out
+    nj = _nj_stage(output_tree_dir, output_site_rates_dir, output_likelihood_dir, msa_dir=msa_dir, families=families,
+                   rate_matrix_path=rate_matrix_path, num_rate_categories=num_rate_categories, max_iters=max_iters,
+                   num_processes=num_processes, remake=remake, verbose=verbose, seed=seed, joiner=joiner, **grid_args)
+    if nni and get_cache_dir() is None:   # (_nj_stage has required the output directories)
+        spr_out.update(output_tree_dir=os.path.join(output_tree_dir, "spr_trees"),
+                       output_likelihood_dir=os.path.join(output_likelihood_dir, "spr_trees"))
     ml = ml_spr_trees(tree_dir=nj["output_tree_dir"], msa_dir=msa_dir, site_rates_dir=nj["output_site_rates_dir"],
                       families=families, rate_matrix_path=rate_matrix_path, num_spr_rounds=num_spr_rounds, spr_radius=spr_radius,
                       num_rounds=num_rounds, **grid_args, **spr_out)
