@@ -25,6 +25,7 @@ from .simulation import simulate_msas  # noqa: F401,E402
 from .estimation import (EStep, RateMatrix, RateMatrixLearner, em_lg, jtt_ipw, quantized_transitions_mle,  # noqa: F401
                          train_quantization)
 from .estimation_end_to_end import lg_end_to_end_with_em_optimizer  # noqa: F401,E402
+from .coevolution import CoevolutionScanner, coevolution_scan, read_coevolution_scan  # noqa: F401,E402
 
 __all__ = [
     "CherryBank", "RateMatrix", "RateMatrixLearner", "train_quantization",
@@ -42,4 +43,5 @@ __all__ = [
     "transfer_distances", "transfer_supports_of_records", "transfer_bootstrap_supports", "nj_transfer_supports",
     "read_transfer_supports", "write_transfer_supports",
     "bootstrap_tree", "ufboot_supports", "read_ufboot_supports", "write_ufboot_supports",
+    "CoevolutionScanner", "coevolution_scan", "read_coevolution_scan",
 ]

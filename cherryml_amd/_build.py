@@ -8,7 +8,8 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 # one translation unit per subsystem (kernels live in the *.hip.h headers each of them includes)
 SRCS = [os.path.join(CSRC, f) for f in ("cherrybank.hip", "cb_bank_fused.hip", "cb_tbasis.hip", "cb_counting.hip", "cb_ble.hip",
                                         "cb_likelihood.hip", "cb_host_io.hip", "cb_simulate.hip", "cb_em.hip",
-                                        "cb_bl.hip", "cb_sr.hip", "cb_nj.hip", "cb_boot.hip", "cb_transfer.hip")]
+                                        "cb_bl.hip", "cb_sr.hip", "cb_nj.hip", "cb_boot.hip", "cb_transfer.hip",
+                                        "cb_coscan.hip")]
 # per-file flags (cb_bank_fused.hip says why)
 FILE_FLAGS = {"cb_bank_fused.hip": ["-mllvm", "-disable-machine-licm"],
               # the simulator's arithmetic is restated in NumPy by the tests: no fused multiply-adds

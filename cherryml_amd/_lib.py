@@ -95,6 +95,9 @@ SIGNATURES = {
     "cb_bl_destroy": (C.c_int, [_vp]),
     "cb_tree_site_rates": (C.c_int, [C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp]),
+    "cb_coscan_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cb_coscan_run": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "cb_coscan_destroy": (C.c_int, [_vp]),
     "cb_siterm_assemble_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp,
                                            C.c_double, C.c_int, C.c_int, _vp, _vp]),
     "cb_siterm_assemble": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int64, _vp, C.c_int64,

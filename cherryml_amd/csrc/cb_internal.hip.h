@@ -1,6 +1,6 @@
 // Shared by the translation units of libcherrybank: error reporting and small host-side helpers.
 // (cherrybank.hip: handle, bank entry points, trainers; cb_bank_fused.hip: the one-launch bank kernel; cb_tbasis.hip: the bank in a
-// time basis; cb_counting.hip; cb_ble.hip; cb_likelihood.hip; cb_host_io.hip; cb_simulate.hip; cb_em.hip; cb_bl.hip; cb_sr.hip; cb_nj.hip; cb_boot.hip; cb_transfer.hip.
+// time basis; cb_counting.hip; cb_ble.hip; cb_likelihood.hip; cb_host_io.hip; cb_simulate.hip; cb_em.hip; cb_bl.hip; cb_sr.hip; cb_nj.hip; cb_boot.hip; cb_transfer.hip; cb_coscan.hip.
 // The tree EM handles' own scaffold -- forest layout, resident buffers, the two passes, the way back of l_u -- is em_layout.h
 // (HIP-free) and em_host.hip.h; what they take from here is cb_test_hook / cb_hook_bytes, CbDevBufs and CbKernelTimer.)
 #pragma once
@@ -97,6 +97,7 @@ int cb_tb_launch_ew(const CbTbEwArgs &a, hipStream_t stream, hipEvent_t stop, in
 //     CB_BANK_KG, CB_BANK_TEST_NO_CLAIM, CB_PHI_Z;
 //   time basis maintenance (cherrybank.hip): CB_TB_TEST_GROWTH, CB_TB_TEST_WARN;
 //   eigensolver (train_host.hip.h, eigh_large_host.hip.h): CB_EIGH_HOST, CB_NO_HYBRID, CB_EIGH_SHORT_PLAN;
+//   the co-evolution scan's pair order (cb_coscan.hip): CB_COSCAN_INDEX_ORDER;
 //   counts (create_host.hip.h): CB_NO_SYM;   faults (cherrybank.hip, train_host.hip.h): CB_FAULT_INJECT;
 //   chunk bounds (cb_hook_bytes below) -- the site-rate scan's candidates (cb_sr.hip): CB_SR_MSG_BYTES; the NNI scan's moves
 //     (cb_bl.hip): CB_NNI_LL_BYTES; the SPR scan's moves (cb_bl.hip): CB_SPR_LL_BYTES; the ancestral reconstruction's nodes (cb_bl.hip): CB_ANC_POST_BYTES; the branch supports'

@@ -794,6 +794,39 @@ int cb_tree_site_rates(int device, int S, const double *Q, const double *pi_root
                        const int *parent, const double *length, const int *n_units, const int8_t *codes, const int *n_cands,
                        const double *cands, const int *current, int *best, double *best_ll, double *ll_all, double *kernel_ms);
 
+/* ---- co-evolution scan: every site pair of a family under the pair model against the product model (S <= 20) ------------------
+ * The first application of a learned co-evolution matrix: which site pairs co-evolve.  For sites i < j of a family and every
+ * sequence pair the co-transition counter walks (cherryml/counting/_count_co_transitions.py:108-140, C++ :359-381; the pairing
+ * of :65-107 is the host's), with bucket q = quantization_idx(len_a + len_b) (cherryml/utils.py:35-56; off-grid pairs are
+ * dropped, no site rates, as in the reference's co-evolution model), states s = x_i S + x_j, e = y_i S + y_j and their
+ * site-swapped versions s', e', the terms are the ones cb_count_co_transitions adds for the contact list {(i, j)}: (s,e), (s',e')
+ * and, when `symmetric`, (e,s), (e',s'); a sequence pair with a negative code at any of its four residues contributes nothing.
+ *   pair_ll [i][j]  = w sum_pairs sum_terms log P2[q][from][to],  P2[q] = expm(grid[q] Q2),  w = 0.25 (symmetric) or 0.5
+ *   indep_ll[i][j]  = the same sum with log P1[q][a][b] + log P1[q][c][d] for a term (a,c) -> (b,d),  P1[q] = expm(grid[q] Q1)
+ *   score           = pair_ll - indep_ll (symmetric, zero diagonal);  n_used = the sequence pairs that contributed (int32)
+ * A bank entry that is not positive has log -inf: score is -inf where only the pair bank meets one, +inf where only the product
+ * does, NaN where both do.
+ *
+ * cb_coscan_create builds both log banks once, on the device, by the library's own expm (pi != NULL: the spectral path of a
+ * reversible Q with that stationary distribution; NULL: scaling and squaring, any rate matrix) with the log taken in place
+ * (165 MB for the pair bank at S = 20, B = 129).  It refuses (CB_EINVAL, the value named) S outside [2, 20], B < 2, a grid that
+ * is not positive and strictly increasing.  With no GPU it fails (CB_EHIP): there is no CPU path.
+ *
+ * cb_coscan_run scans n_fam families in one launch: family f has L[f] sites and n_pairs[f] cb_count_pair records (the families'
+ * records concatenated; seq_a / seq_b are byte offsets of L[f] int8 codes in `seqs`, len_a + len_b is the pair's length; aux and n
+ * are not read).  The outputs are the families' [L][L] matrices concatenated.  kernel_ms (may be NULL) receives the scan
+ * kernel's device time.  It refuses (CB_EINVAL, the value named, the handle stays usable) L[f] < 1, a sequence offset beyond
+ * seqs_bytes, a code outside [-1, S).  Every site pair is summed by one thread over its family's sequence pairs in one fixed
+ * order (by bucket, ties by pair index), without atomics: two calls, two handles, and a family alone or among others give
+ * bitwise-equal results.  One call at a time per handle. */
+typedef struct cb_coscan_s *cb_coscan;
+int cb_coscan_create(int device, int S, int B, const double *grid, const double *Q1, const double *pi1, const double *Q2,
+                     const double *pi2, cb_coscan *out);
+int cb_coscan_run(cb_coscan h, int n_fam, const int *L, const int8_t *seqs, int64_t seqs_bytes, const cb_count_pair *pairs,
+                  const int64_t *n_pairs, int symmetric, double *score, double *pair_ll, double *indep_ll, int *n_used,
+                  double *kernel_ms);
+int cb_coscan_destroy(cb_coscan h);
+
 /* ---- FastCherries' cherry pairing, host only -------------------------------------------------------------
  * divide_and_pair of phylogeny_estimation/FastCherries/pairing_algorithms.cpp:77-175 on int8 sequences
  * [n][L] (state index, -1 unknown): the seeded divide-and-conquer over Hamming distances, with the
